@@ -16,12 +16,13 @@ import time
 
 
 def canned_chat_response(model: str = "bench-llm", prompt_tokens: int = 4096,
-                         completion_tokens: int = 16) -> bytes:
+                         completion_tokens: int = 16,
+                         created: int | None = None) -> bytes:
     body = json.dumps(
         {
             "id": "chatcmpl-bench",
             "object": "chat.completion",
-            "created": int(time.time()),
+            "created": int(time.time()) if created is None else created,
             "model": model,
             "choices": [
                 {

@@ -21,6 +21,27 @@ state — short timed regions under-report by ~30% because connection
 pools, GC state, and the GPU admission pipeline are still cold
 (round-1 finding: 20×1-wave steps measured 49.8k on a config that
 sustains 72.8k over 9.6M requests).
+
+The harness confines itself to the CPUs of one NUMA node (the GPU's,
+when known) before it starts any thread, so the rate does not move with
+where the scheduler happens to place the loopback peers; ``--no-pin``
+leaves the affinity alone (figures in ``_pin_to_numa_node``).
+
+The ``metric`` string names two things; the request rate is ``value``,
+and the latency half (``config.p50_added_latency_ms``) is filled only
+with ``--full``. If the native extension cannot be imported a plain run
+still falls back to the Python lean front, visible only as
+``config.front == "lean"`` — compare builds on ``front == "fast"``;
+``--dump-outputs`` refuses that fallback.
+
+A plain run does only what the headline figure needs: set up, warm up,
+time the K steps, print the line. ``--full`` adds the secondary
+measurements (the warm direct-to-upstream latency baseline behind
+``p50_added_latency_ms``; the state-sync tick timing on multi-rank runs).
+``--dump-outputs DIR`` writes what the timed path produced in its last
+step as ``DIR/<name>.npy`` (see ``dump_outputs``); the payloads, the
+tokenizer tables and the upstream's canned body are fixed, so two builds
+can be compared output for output.
 """
 
 from __future__ import annotations
@@ -40,6 +61,45 @@ WORDS = (
     "profile matrix kernels on a liquid cooled accelerator node during the "
     "long afternoon of benchmark season"
 ).split()
+
+# `created` stamp of the mock upstream's canned completion (fixed, so the
+# bytes the gateway relays are identical from run to run)
+BENCH_CREATED = 1700000000
+
+# server-side accounting counters written by --dump-outputs, in file order
+DUMP_COUNTERS = ("requests", "responses_2xx", "gpu_tokens", "input_tokens",
+                 "output_tokens", "total_tokens", "bytes_in", "bytes_out",
+                 "cache_hits", "cache_misses")
+
+
+def dump_outputs(out_dir: str, bodies: list, stats0: dict, stats1: dict,
+                 steps: int) -> None:
+    """Write what the timed path produced as float64 .npy files.
+
+    responses.npy  [connections, max_len]: the response body every client
+        connection received for the FINAL request of the last timed step,
+        one byte value per element, rows padded with -1.
+    response_lengths.npy  [connections]: body length per row.
+    accounting_per_step.npy  [len(DUMP_COUNTERS)]: the gateway's counters
+        (requests served, GPU-counted prompt tokens, usage tokens charged,
+        bytes relayed, semantic-cache hits/misses) accumulated over the
+        timed region, per step. Every step issues the same requests, so
+        the per-step figure is the region total over --steps.
+    A few hundred KB at the default sizes (one short completion body per
+    connection), far below any size that would need sampling."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    width = max((len(b) for b in bodies), default=0)
+    resp = np.full((len(bodies), width), -1.0, dtype=np.float64)
+    for i, b in enumerate(bodies):
+        resp[i, : len(b)] = np.frombuffer(b, dtype=np.uint8)
+    np.save(os.path.join(out_dir, "responses.npy"), resp)
+    np.save(os.path.join(out_dir, "response_lengths.npy"),
+            np.array([len(b) for b in bodies], dtype=np.float64))
+    acct = np.array([(stats1[k] - stats0[k]) / steps for k in DUMP_COUNTERS],
+                    dtype=np.float64)
+    np.save(os.path.join(out_dir, "accounting_per_step.npy"), acct)
 
 
 def _gpu_device(local_rank: int) -> int:
@@ -186,21 +246,24 @@ async def worker_main(args, local_rank: int, ready, go, out_q):
     path = "/v1/chat/completions"
     counter = [0]
 
-    # warm both paths, then record the warm direct-to-upstream baseline.
+    # warm the gateway path; --full also warms the direct path and records
+    # the warm direct-to-upstream baseline.
     # Warmup is wave-scaled like the timed steps: the lean client's pools,
     # GC steady state and the GPU admission pipeline need hundreds of
     # waves before the shard reaches its sustained rate.
     waves = max(args.waves, 1)
     scratch: list[float] = []
-    for _ in range(max(args.warmup, 1)):
-        await fire_step(client, up_port, path, payloads, args.batch, scratch,
-                        waves=min(waves, 10))
+    if args.full:
+        for _ in range(max(args.warmup, 1)):
+            await fire_step(client, up_port, path, payloads, args.batch,
+                            scratch, waves=min(waves, 10))
     for _ in range(args.warmup):
         await fire_step(client, gw_port, path, payloads, args.batch, scratch,
                         counter, waves=waves)
     direct_lat: list[float] = []
-    await fire_step(client, up_port, path, payloads, args.batch, direct_lat,
-                    waves=5)
+    if args.full:
+        await fire_step(client, up_port, path, payloads, args.batch,
+                        direct_lat, waves=5)
     if use_gpu:
         torch.cuda.synchronize()
 
@@ -223,7 +286,7 @@ async def worker_main(args, local_rank: int, ready, go, out_q):
             "requests": args.steps * waves * args.batch,
             "p50": statistics.median(lat),
             "p99": sorted(lat)[max(int(len(lat) * 0.99) - 1, 0)],
-            "p50_direct": statistics.median(direct_lat),
+            "p50_direct": statistics.median(direct_lat) if direct_lat else None,
         }
     )
     await client.close()
@@ -276,15 +339,17 @@ def loadgen_entry(args, gw_port, direct_port, ready, go, out_q):
         path = "/v1/chat/completions"
         waves = max(args.waves, 1)
         scratch: list[float] = []
-        for _ in range(max(args.warmup, 1)):
-            await fire_step(client, direct_port, path, payloads, args.batch,
-                            scratch, waves=min(waves, 10))
+        if args.full:
+            for _ in range(max(args.warmup, 1)):
+                await fire_step(client, direct_port, path, payloads,
+                                args.batch, scratch, waves=min(waves, 10))
         for _ in range(args.warmup):
             await fire_step(client, gw_port, path, payloads, args.batch,
                             scratch, waves=waves)
         direct_lat: list[float] = []
-        await fire_step(client, direct_port, path, payloads, args.batch,
-                        direct_lat, waves=5)
+        if args.full:
+            await fire_step(client, direct_port, path, payloads, args.batch,
+                            direct_lat, waves=5)
 
         ready.set()
         while not go.is_set():
@@ -302,7 +367,7 @@ def loadgen_entry(args, gw_port, direct_port, ready, go, out_q):
                 "requests": args.steps * waves * args.batch,
                 "p50": statistics.median(lat),
                 "p99": sorted(lat)[max(int(len(lat) * 0.99) - 1, 0)],
-                "p50_direct": statistics.median(direct_lat),
+                "p50_direct": statistics.median(direct_lat) if direct_lat else None,
             }
         )
         await client.close()
@@ -497,6 +562,71 @@ def _cpu_quota() -> int:
     return os.cpu_count() or 8
 
 
+def _parse_cpulist(text: str) -> set:
+    cpus = set()
+    for part in text.strip().split(","):
+        if part:
+            lo, _, hi = part.partition("-")
+            cpus.update(range(int(lo), int(hi or lo) + 1))
+    return cpus
+
+
+def _pin_to_numa_node(device) -> str | None:
+    """Confine the harness to the CPUs of ONE NUMA node (the GPU's when
+    the PCI topology names it, else the node with most usable CPUs).
+    Gateway, mock upstream and load generator talk over loopback; left to
+    the scheduler their threads land on both sockets and the rate moves
+    with the placement, too much for two runs to be compared. Alternating
+    runs at --steps 20 --warmup 5, six each: 125.4-127.1k req/s with the
+    pin (p99 1.1-1.4 ms), 111.3-119.8k with --no-pin (p99 1.8-4.8 ms).
+    Returns a description for the result line; None when nothing was
+    pinned (one node, or a node with fewer CPUs than the quota)."""
+    import glob
+
+    allowed = os.sched_getaffinity(0)
+    nodes = {}
+    for path in glob.glob("/sys/devices/system/node/node[0-9]*/cpulist"):
+        cpus = _parse_cpulist(open(path).read()) & allowed
+        if cpus:
+            nodes[int(path.split("/")[-2][4:])] = cpus
+    if len(nodes) < 2:
+        return None
+    node = None
+    if device is not None:
+        try:
+            p = torch.cuda.get_device_properties(device)
+            bdf = "%04x:%02x:%02x.0" % (p.pci_domain_id, p.pci_bus_id,
+                                        p.pci_device_id)
+            node = int(open(f"/sys/bus/pci/devices/{bdf}/numa_node").read())
+        except (AttributeError, OSError, ValueError):
+            pass
+    if node not in nodes:
+        node = max(sorted(nodes), key=lambda n: len(nodes[n]))
+    if len(nodes[node]) < _cpu_quota():
+        return None
+    # runtime threads that already exist do not inherit a new mask
+    for tid in os.listdir("/proc/self/task"):
+        try:
+            os.sched_setaffinity(int(tid), nodes[node])
+        except OSError:  # the thread has exited since the listing
+            pass
+    return f"numa node {node} ({len(nodes[node])} cpus)"
+
+
+def _settled_stats(front) -> dict:
+    """The front's counters once they have stopped moving: the server
+    threads bump them after the client already has its response, so a
+    read straight after a load run can miss the last increments (and a
+    read straight before the next would then count them there)."""
+    stats = front.stats()
+    for _ in range(200):
+        time.sleep(0.005)
+        prev, stats = stats, front.stats()
+        if stats == prev and stats["active_connections"] == 0:
+            break
+    return stats
+
+
 def run_native_bench(args, rank, world, local_rank, use_gpu, barrier_sync):
     """Single-process native harness: C++ mock upstream + C++ gateway
     (with in-process HIP admission) + C++ closed-loop load generator —
@@ -513,7 +643,10 @@ def run_native_bench(args, rank, world, local_rank, use_gpu, barrier_sync):
         canned = canned_chat_sse(prompt_tokens=args.tokens,
                                  n_chunks=args.stream_chunks)
     else:
-        canned = canned_chat_response(prompt_tokens=args.tokens)
+        # fixed `created` stamp: the upstream body is a benchmark INPUT and
+        # must be byte-identical from run to run (--dump-outputs)
+        canned = canned_chat_response(prompt_tokens=args.tokens,
+                                      created=BENCH_CREATED)
     mock = aigw_fast.FastMock()
     up_port = mock.start("127.0.0.1", canned.decode("latin1"))
     gpu_direct = use_gpu
@@ -559,29 +692,37 @@ def run_native_bench(args, rank, world, local_rank, use_gpu, barrier_sync):
     waves = max(args.waves, 1)
     path = "/v1/chat/completions"
 
-    # warmup (gateway) then warm direct baseline
+    # warmup (gateway); --full also records the warm direct-to-upstream
+    # baseline that p50_added_latency_ms is measured against
     aigw_fast.run_load_pool("127.0.0.1", gw_port, path, payloads, conns,
                             max(args.warmup, 1) * waves)
-    direct = aigw_fast.run_load_pool("127.0.0.1", up_port, path, payloads,
-                                     conns, 5)
+    direct = None
+    if args.full:
+        direct = aigw_fast.run_load_pool("127.0.0.1", up_port, path, payloads,
+                                         conns, 5)
     if use_gpu:
         torch.cuda.synchronize()
 
+    dump = bool(args.dump_outputs) and rank == 0
+    stats0 = _settled_stats(front) if dump else None
     barrier_sync()
     t0 = time.perf_counter()
     res = aigw_fast.run_load_pool("127.0.0.1", gw_port, path, payloads, conns,
-                                  args.steps * waves)
+                                  args.steps * waves, capture_last=dump)
     if use_gpu:
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     barrier_sync()
     assert res["errors"] == 0, f"load errors: {res}"
+    if dump:
+        dump_outputs(args.dump_outputs, res["last_bodies"], stats0,
+                     _settled_stats(front), args.steps)
     row = {
         "elapsed": elapsed,
         "requests": res["completed"],
         "p50": res["p50_ms"],
         "p99": res["p99_ms"],
-        "p50_direct": direct["p50_ms"],
+        "p50_direct": direct["p50_ms"] if direct else None,
     }
     mock.stop()
     return row, elapsed, workers, front
@@ -638,12 +779,33 @@ def main():
                          "@40w measured) at higher p50; direct contexts win "
                          "at the ~12 workers/shard an 8-rank node affords "
                          "(38k req/s, 5.8 ms added)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path "
+                         "produced in its last step (response bodies, "
+                         "per-step gateway accounting) as DIR/<name>.npy; "
+                         "native harness only")
+    ap.add_argument("--no-pin", action="store_true",
+                    help="leave the CPU affinity alone (default: confine "
+                         "the harness to one NUMA node, see "
+                         "_pin_to_numa_node)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements: the warm "
+                         "direct-to-upstream latency baseline "
+                         "(p50_direct_ms, p50_added_latency_ms) and, on "
+                         "multi-rank runs, the state-sync tick timing")
     args = ap.parse_args()
+    if args.dump_outputs and not (args.front == "fast"
+                                  and args.harness == "native"):
+        ap.error("--dump-outputs needs --front fast --harness native")
 
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
     local_rank = int(os.environ.get("LOCAL_RANK", rank))
     use_gpu = torch.cuda.is_available()
+    cpu_affinity = None
+    if not args.no_pin:
+        cpu_affinity = _pin_to_numa_node(
+            _gpu_device(local_rank) if use_gpu and not args.no_gpu else None)
     if world > 1:
         backend = "nccl" if use_gpu else "gloo"
         # AIGW_BENCH_BACKEND=gloo lets a multi-rank run share ONE GPU
@@ -675,6 +837,8 @@ def main():
             results = [row]
             native = True
         except ImportError:
+            if args.dump_outputs:
+                raise
             fast_mode = False
     elif fast_mode:
         try:
@@ -734,7 +898,7 @@ def main():
             p.terminate()
 
     statesync_tick_us = None
-    if world > 1:
+    if world > 1 and args.full:
         # demonstrate the RCCL-synced rate-limit counters on the same
         # communicator the scale bench uses (BASELINE config: "RCCL-synced
         # rate-limit counters"): a fixed number of fused all-reduce ticks
@@ -762,6 +926,7 @@ def main():
         for _ in range(20):
             sync.tick_sync()
         statesync_tick_us = (time.perf_counter() - ts0) / 20 * 1e6
+    if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64)
         if torch.distributed.get_backend() == "nccl":
             t = t.cuda()
@@ -774,7 +939,8 @@ def main():
     value = total_requests / elapsed_max
     p50 = statistics.median(r["p50"] for r in results)
     p99 = max(r["p99"] for r in results)
-    p50_direct = statistics.median(r["p50_direct"] for r in results)
+    p50_direct = (statistics.median(r["p50_direct"] for r in results)
+                  if args.full else None)
 
     if rank == 0:
         out = {
@@ -799,10 +965,12 @@ def main():
                 "front": "fast" if fast_mode else "lean",
                 "streamed": bool(getattr(args, "stream", False)) or None,
                 "workers_per_shard": workers,
+                "cpu_affinity": cpu_affinity,
                 "p50_ms": round(p50, 3),
                 "p99_ms": round(p99, 3),
-                "p50_direct_ms": round(p50_direct, 3),
-                "p50_added_latency_ms": round(p50 - p50_direct, 3),
+                "p50_direct_ms": round(p50_direct, 3) if args.full else None,
+                "p50_added_latency_ms": (round(p50 - p50_direct, 3)
+                                         if args.full else None),
                 "gpu_token_accounting": use_gpu,
                 "gpu_admission": (
                     dict(zip(("batches", "texts", "time_us", "max_us",

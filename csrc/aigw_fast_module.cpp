@@ -45,13 +45,14 @@ PYBIND11_MODULE(aigw_fast, m) {
   m.def(
       "run_load_pool",
       [](const std::string& host, uint16_t port, const std::string& path,
-         py::list bodies, int connections, int per_conn) {
+         py::list bodies, int connections, int per_conn, bool capture_last) {
         std::vector<std::string> pool;
         for (auto b : bodies) pool.push_back(b.cast<py::bytes>());
         LoadResult r;
         {
           py::gil_scoped_release release;
-          r = run_load_pool(host, port, path, pool, connections, per_conn);
+          r = run_load_pool(host, port, path, pool, connections, per_conn,
+                            capture_last);
         }
         py::dict d;
         d["elapsed_s"] = r.elapsed_s;
@@ -59,11 +60,18 @@ PYBIND11_MODULE(aigw_fast, m) {
         d["errors"] = r.errors;
         d["p50_ms"] = r.p50_ms;
         d["p99_ms"] = r.p99_ms;
+        if (capture_last) {
+          py::list last;
+          for (const auto& b : r.last_bodies) last.append(py::bytes(b));
+          d["last_bodies"] = last;
+        }
         return d;
       },
       py::arg("host"), py::arg("port"), py::arg("path"), py::arg("bodies"),
       py::arg("connections"), py::arg("per_conn"),
-      "run_load with a cycling body pool (semantic-cache hit mixes)");
+      py::arg("capture_last") = false,
+      "run_load with a cycling body pool (semantic-cache hit mixes); "
+      "capture_last also returns each connection's final response body");
 
   py::class_<FastServer>(m, "FastServer")
       .def(py::init<>())

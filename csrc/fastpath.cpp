@@ -1812,7 +1812,7 @@ void FastMock::serve(int fd) {
 LoadResult run_load_pool(const std::string& host, uint16_t port,
                          const std::string& path,
                          const std::vector<std::string>& bodies,
-                         int connections, int per_conn) {
+                         int connections, int per_conn, bool capture_last) {
   std::vector<std::string> reqs;
   reqs.reserve(bodies.size());
   for (const auto& body : bodies)
@@ -1821,6 +1821,7 @@ LoadResult run_load_pool(const std::string& host, uint16_t port,
                    std::to_string(body.size()) + "\r\n\r\n" + body);
   std::vector<std::thread> threads;
   std::vector<std::vector<int64_t>> lat(connections);
+  std::vector<std::string> last(capture_last ? connections : 0);
   std::atomic<uint64_t> errors{0};
   std::atomic<uint64_t> completed{0};
   int64_t t0 = now_us();
@@ -1866,17 +1867,22 @@ LoadResult run_load_pool(const std::string& host, uint16_t port,
           chunked = t != std::string::npos && t < head_end;
         }
         bool ok = buf.compare(9, 3, "200") == 0;
+        std::string* keep =
+            capture_last && i == per_conn - 1 ? &last[c] : nullptr;
         if (chunked) {
           // streamed response (SSE): consume chunked framing to the
           // terminal chunk so the connection stays reusable
           buf.erase(0, head_end + 4);
           ChunkedParser cp;
-          cp.feed(buf.data(), buf.size(), [](const char*, size_t) {});
+          auto sink = [keep](const char* d, size_t n) {
+            if (keep) keep->append(d, n);
+          };
+          cp.feed(buf.data(), buf.size(), sink);
           buf.clear();
           while (!cp.done() && !cp.error()) {
             ssize_t r = read_some(fd, tmp, sizeof(tmp));
             if (r <= 0) { fail = true; break; }
-            cp.feed(tmp, (size_t)r, [](const char*, size_t) {});
+            cp.feed(tmp, (size_t)r, sink);
           }
           if (fail || cp.error()) { ::close(fd); fd = -1; errors++; continue; }
         } else {
@@ -1886,6 +1892,7 @@ LoadResult run_load_pool(const std::string& host, uint16_t port,
             buf.append(tmp, (size_t)r);
           }
           if (fail) { ::close(fd); fd = -1; errors++; continue; }
+          if (keep) keep->assign(buf, head_end + 4, (size_t)clen);
           buf.erase(0, head_end + 4 + (size_t)clen);
         }
         if (!ok) { errors++; continue; }
@@ -1900,6 +1907,7 @@ LoadResult run_load_pool(const std::string& host, uint16_t port,
   out.elapsed_s = (double)(now_us() - t0) / 1e6;
   out.completed = completed.load();
   out.errors = errors.load();
+  out.last_bodies = std::move(last);
   std::vector<int64_t> all;
   for (auto& v : lat) all.insert(all.end(), v.begin(), v.end());
   if (!all.empty()) {

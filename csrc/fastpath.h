@@ -213,6 +213,9 @@ struct LoadResult {
   uint64_t completed = 0;
   uint64_t errors = 0;
   double p50_ms = 0, p99_ms = 0;
+  // capture_last only: per connection, the body of the response to its
+  // final request (de-chunked for streamed responses)
+  std::vector<std::string> last_bodies;
 };
 
 LoadResult run_load(const std::string& host, uint16_t port,
@@ -221,6 +224,7 @@ LoadResult run_load(const std::string& host, uint16_t port,
 LoadResult run_load_pool(const std::string& host, uint16_t port,
                          const std::string& path,
                          const std::vector<std::string>& bodies,
-                         int connections, int per_conn);
+                         int connections, int per_conn,
+                         bool capture_last = false);
 
 }  // namespace aigw_fast

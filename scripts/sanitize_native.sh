@@ -4,7 +4,11 @@
 # CPU-only; runs in seconds. Invoked by tests/test_native_sanitize.py.
 set -euo pipefail
 cd "$(dirname "$0")/.."
-out="${TMPDIR:-/tmp}/aigw_native_core_test"
+# private scratch directory: a fixed name under /tmp collides with a
+# binary left there by another user
+tmp="$(mktemp -d)"
+trap 'rm -rf "$tmp"' EXIT
+out="$tmp/aigw_native_core_test"
 g++ -std=c++17 -O1 -g -fno-omit-frame-pointer \
     -fsanitize=address,undefined -fno-sanitize-recover=all \
     -D_GLIBCXX_ASSERTIONS \
@@ -14,7 +18,7 @@ g++ -std=c++17 -O1 -g -fno-omit-frame-pointer \
 # the native data-plane server (csrc/fastpath.cpp), GPU admission
 # stubbed: concurrent clients + hot route swaps + retries + rate limits
 # under ASan/UBSan
-out2="${TMPDIR:-/tmp}/aigw_fastpath_sanitize_test"
+out2="$tmp/aigw_fastpath_sanitize_test"
 g++ -std=c++17 -O1 -g -fno-omit-frame-pointer \
     -fsanitize=address,undefined -fno-sanitize-recover=all \
     -D_GLIBCXX_ASSERTIONS \

@@ -15,13 +15,18 @@ def test_torchrun_dp2_bench():
     env = dict(os.environ)
     env["PYTHONPATH"] = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     repo = env["PYTHONPATH"]
+    # CPU + gloo also where a GPU is present: two ranks cannot share one
+    # device under RCCL, and this test is about the launch path
+    env["CUDA_VISIBLE_DEVICES"] = ""
+    env["HIP_VISIBLE_DEVICES"] = ""
+    env["AIGW_BENCH_BACKEND"] = "gloo"
     proc = subprocess.run(
         [
             sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
             "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
             "--master-port", "29733", os.path.join(repo, "bench.py"),
             "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8",
-            "--workers", "1", "--waves", "2", "--upstreams", "1",
+            "--workers", "1", "--waves", "2", "--upstreams", "1", "--full",
         ],
         env=env,
         capture_output=True,
