@@ -83,9 +83,20 @@ __global__ void f32_to_bf16_kernel(const float* __restrict__ in,
   if (i < n) out[i] = (bf16)in[i];
 }
 
+// Token-position flags for the compaction that feeds the token-dense
+// meanpool: out_ids is pre-filled with -1 on the cache path, so byte
+// position i carries a token iff out_ids[i] >= 0.
+__global__ void tok_flags_kernel(const int32_t* __restrict__ out_ids, int n,
+                                 uint8_t* __restrict__ flags) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) flags[i] = out_ids[i] >= 0;
+}
+
 // Token-dense meanpool: iterate the COMPACTED token list (ghead[j] =
 // byte position of token j, request r owns [req_excl[r],
 // req_excl[r]+counts[r])) instead of scanning every byte for -1 holes.
+// submit_cache() builds that list (it reuses the group-head buffer once
+// the BPE kernel has consumed the group heads).
 // The byte-indexed version (cache_kernels.cuh meanpool_accum_kernel,
 // still used by the torch-tensor path) walked ~25k bytes per request to
 // touch ~4k tokens and measured 808 us/batch = 63% of cache-mode GPU
@@ -315,7 +326,7 @@ class GpuAdmissionDirect {
     hipLaunchKernelGGL(seg_flags_kernel, dim3(blocks), dim3(256), 0, st,
                        b.d_bytes, (int)n, b.d_flags);
     hipLaunchKernelGGL(seg_force_starts_kernel, dim3((n_req + 255) / 256),
-                       dim3(256), 0, st, b.d_off, n_req, b.d_flags);
+                       dim3(256), 0, st, b.d_off, n_req, (int)n, b.d_flags);
     hipLaunchKernelGGL(seg_block_count_kernel, dim3(blocks), dim3(256), 0,
                        st, b.d_flags, (int)n, b.d_blk);
     hipLaunchKernelGGL(excl_scan_kernel, dim3(1), dim3(256), 0, st,
@@ -335,6 +346,11 @@ class GpuAdmissionDirect {
     hipLaunchKernelGGL(flag_compact_write_kernel, dim3(blocks), dim3(256), 0,
                        st, b.d_gflags, (int)n, b.d_excl, b.d_ghead);
     HIP_OK(hipMemsetAsync(b.d_counts, 0, sizeof(int32_t) * n_req, st));
+    bool want_cache = pending_slots != nullptr && cache_on_;
+    // the cache pipeline finds tokens by out_ids >= 0: merged-away byte
+    // positions must read -1, not whatever the previous batch left there
+    if (want_cache)
+      HIP_OK(hipMemsetAsync(b.d_out_ids, 0xFF, sizeof(int32_t) * n, st));
     long long group_bound = (long long)n / 32 + n_req + 1;
     int blocks2 = (int)((group_bound + 3) / 4);
     hipLaunchKernelGGL(bpe_encode_grouped_dev_kernel, dim3(blocks2), dim3(256),
@@ -342,7 +358,7 @@ class GpuAdmissionDirect {
                        b.d_totals, (int)n, b.d_ghead, b.d_totals + 1,
                        d_htab_keys_, d_htab_rank_, htab_mask_, b.d_out_ids,
                        b.d_counts);
-    if (pending_slots != nullptr && cache_on_) {
+    if (want_cache) {
       if (!submit_cache(b, n, n_req, pending_slots)) return false;
     }
     HIP_OK(hipMemcpyAsync(b.h_counts, b.d_counts, sizeof(int32_t) * n_req,
@@ -445,6 +461,18 @@ class GpuAdmissionDirect {
     HIP_OK(hipMemsetAsync(b.d_pool, 0, sizeof(float) * (size_t)n_req * dim, st));
     HIP_OK(hipMemsetAsync(b.d_poolcnt, 0, sizeof(int32_t) * n_req, st));
     constexpr int P = 32;
+    // compact the token byte positions into d_ghead (ordered, so request
+    // r's tokens are the d_counts[r] entries from d_req_excl[r]); the
+    // group heads it held were last read by the BPE kernel above
+    int tblocks = (int)((n + 255) / 256);
+    hipLaunchKernelGGL(tok_flags_kernel, dim3(tblocks), dim3(256), 0, st,
+                       b.d_out_ids, (int)n, b.d_gflags);
+    hipLaunchKernelGGL(seg_block_count_kernel, dim3(tblocks), dim3(256), 0, st,
+                       b.d_gflags, (int)n, b.d_blk);
+    hipLaunchKernelGGL(excl_scan_kernel, dim3(1), dim3(256), 0, st,
+                       b.d_blk, tblocks, b.d_excl, b.d_req_excl + max_req_);
+    hipLaunchKernelGGL(flag_compact_write_kernel, dim3(tblocks), dim3(256), 0,
+                       st, b.d_gflags, (int)n, b.d_excl, b.d_ghead);
     hipLaunchKernelGGL(excl_scan_kernel, dim3(1), dim3(256), 0, st,
                        b.d_counts, n_req, b.d_req_excl,
                        b.d_req_excl + max_req_);

@@ -6,13 +6,165 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <cstdint>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
 #include "fastpath.h"
 
 namespace py = pybind11;
 using namespace aigw_fast;
 
+namespace aigw_fast {
+
+// admission.hip entry points (same declarations as fastpath.cpp)
+GpuAdmissionDirect* admission_create(const long long* htab_keys,
+                                     const int32_t* htab_rank, int htab_n,
+                                     size_t max_bytes, int max_req, int device);
+bool admission_count(GpuAdmissionDirect* a, const char* bytes, size_t n,
+                     const int64_t* offsets, int n_req, int32_t* counts_out);
+void admission_destroy(GpuAdmissionDirect* a);
+bool admission_init_cache(GpuAdmissionDirect* a, const uint16_t* emb, int vocab,
+                          const uint16_t* proj, int dim, long long capacity,
+                          float threshold, int pending_cap, bool fp8);
+bool admission_count_lookup(GpuAdmissionDirect* a, const char* bytes, size_t n,
+                            const int64_t* offsets, int n_req,
+                            int32_t* counts_out, const int32_t* pending_slots,
+                            int32_t* rows_out, float* scores_out);
+long long admission_cache_insert(GpuAdmissionDirect* a, int pending_slot);
+
+}  // namespace aigw_fast
+
+namespace {
+
+// Direct test seam over the native admission path: the same C entry
+// points the server's batcher uses, one synchronous batch per call, no
+// HTTP and no threads. Adds no kernels and no behaviour of its own.
+class AdmissionProbe {
+ public:
+  AdmissionProbe(py::buffer htab_keys, py::buffer htab_rank, size_t max_bytes,
+                 int max_req, int device)
+      : max_bytes_(max_bytes), max_req_(max_req) {
+    py::buffer_info ki = htab_keys.request();
+    py::buffer_info ri = htab_rank.request();
+    if (ki.itemsize != 8 || ri.itemsize != 4)
+      throw std::runtime_error("htab_keys must be int64, htab_rank int32");
+    if (ki.size != ri.size || ki.size <= 0 || (ki.size & (ki.size - 1)) != 0)
+      throw std::runtime_error("htab arrays must share a power-of-two length");
+    if (max_bytes == 0 || max_req <= 0)
+      throw std::runtime_error("max_bytes and max_req must be positive");
+    adm_ = admission_create(static_cast<const long long*>(ki.ptr),
+                            static_cast<const int32_t*>(ri.ptr), (int)ki.size,
+                            max_bytes, max_req, device);
+    if (adm_ == nullptr) throw std::runtime_error("admission init failed");
+  }
+  AdmissionProbe(const AdmissionProbe&) = delete;
+  AdmissionProbe& operator=(const AdmissionProbe&) = delete;
+  ~AdmissionProbe() {
+    if (adm_ != nullptr) admission_destroy(adm_);
+  }
+
+  void init_cache(py::buffer emb, py::buffer proj, long long capacity,
+                  float threshold, int pending_cap, bool fp8) {
+    constexpr int dim = 384;  // the native cache's one tuned top-k shape
+    py::buffer_info ei = emb.request();
+    py::buffer_info pi = proj.request();
+    if (ei.itemsize != 2 || pi.itemsize != 2)
+      throw std::runtime_error("emb/proj must be bf16 (uint16 view)");
+    int vocab = (int)(ei.size / dim);
+    if (vocab <= 0 || (long long)vocab * dim != ei.size ||
+        pi.size != (long long)dim * dim)
+      throw std::runtime_error("emb/proj shape mismatch");
+    if (capacity <= 0 || pending_cap <= 0)
+      throw std::runtime_error("capacity and pending_cap must be positive");
+    if (cache_on_) throw std::runtime_error("cache already initialised");
+    if (!admission_init_cache(adm_, static_cast<const uint16_t*>(ei.ptr), vocab,
+                              static_cast<const uint16_t*>(pi.ptr), dim,
+                              capacity, threshold, pending_cap, fp8))
+      throw std::runtime_error("native cache init failed");
+    pending_cap_ = pending_cap;
+    cache_on_ = true;
+  }
+
+  std::vector<int32_t> count(const std::vector<std::string>& texts) {
+    pack(texts);
+    std::vector<int32_t> counts(texts.size(), 0);
+    bool ok;
+    {
+      py::gil_scoped_release release;
+      ok = admission_count(adm_, bytes_.data(), bytes_.size(), offs_.data(),
+                           (int)texts.size(), counts.data());
+    }
+    if (!ok) throw std::runtime_error("admission_count failed");
+    return counts;
+  }
+
+  py::tuple count_lookup(const std::vector<std::string>& texts) {
+    if (!cache_on_) throw std::runtime_error("init_cache() first");
+    if ((long long)texts.size() > pending_cap_)
+      throw std::runtime_error("more texts than pending slots");
+    pack(texts);
+    size_t nt = texts.size();
+    std::vector<int32_t> counts(nt, 0), rows(nt, -1), slots(nt);
+    std::vector<float> scores(nt, 0.f);
+    for (size_t i = 0; i < nt; ++i) slots[i] = (int32_t)i;
+    bool ok;
+    {
+      py::gil_scoped_release release;
+      ok = admission_count_lookup(adm_, bytes_.data(), bytes_.size(),
+                                  offs_.data(), (int)nt, counts.data(),
+                                  slots.data(), rows.data(), scores.data());
+    }
+    if (!ok) throw std::runtime_error("admission_count_lookup failed");
+    return py::make_tuple(counts, rows, scores);
+  }
+
+  long long insert(int slot) {
+    if (!cache_on_) throw std::runtime_error("init_cache() first");
+    long long row = admission_cache_insert(adm_, slot);
+    if (row < 0) throw std::runtime_error("cache insert failed");
+    return row;
+  }
+
+ private:
+  void pack(const std::vector<std::string>& texts) {
+    if (texts.empty() || (long long)texts.size() > max_req_)
+      throw std::runtime_error("text count out of range");
+    bytes_.clear();
+    offs_.clear();
+    for (const auto& t : texts) {
+      offs_.push_back((int64_t)bytes_.size());
+      bytes_.append(t);
+    }
+    if (bytes_.empty() || bytes_.size() > max_bytes_)
+      throw std::runtime_error("batch bytes out of range");
+  }
+
+  GpuAdmissionDirect* adm_ = nullptr;
+  size_t max_bytes_;
+  int max_req_;
+  int pending_cap_ = 0;
+  bool cache_on_ = false;
+  std::string bytes_;
+  std::vector<int64_t> offs_;
+};
+
+}  // namespace
+
 PYBIND11_MODULE(aigw_fast, m) {
   m.doc() = "aigw native data-plane fast path";
+
+  py::class_<AdmissionProbe>(m, "AdmissionProbe")
+      .def(py::init<py::buffer, py::buffer, size_t, int, int>(),
+           py::arg("htab_keys"), py::arg("htab_rank"), py::arg("max_bytes"),
+           py::arg("max_req"), py::arg("device") = 0)
+      .def("init_cache", &AdmissionProbe::init_cache, py::arg("emb_u16"),
+           py::arg("proj_u16"), py::arg("capacity"), py::arg("threshold"),
+           py::arg("pending_cap"), py::arg("fp8"))
+      .def("count", &AdmissionProbe::count, py::arg("texts"))
+      .def("count_lookup", &AdmissionProbe::count_lookup, py::arg("texts"))
+      .def("insert", &AdmissionProbe::insert, py::arg("slot"));
 
   py::class_<FastMock>(m, "FastMock")
       .def(py::init<>())

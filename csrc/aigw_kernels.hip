@@ -74,7 +74,7 @@ std::vector<at::Tensor> bpe_segment(at::Tensor bytes, at::Tensor req_off) {
                      bytes.data_ptr<uint8_t>(), n, flags.data_ptr<uint8_t>());
   int n_req = (int)req_off.numel();
   hipLaunchKernelGGL(seg_force_starts_kernel, dim3((n_req + 255) / 256), dim3(256), 0,
-                     stream, req_off.data_ptr<int64_t>(), n_req,
+                     stream, req_off.data_ptr<int64_t>(), n_req, n,
                      flags.data_ptr<uint8_t>());
   at::Tensor blk_counts = at::empty({blocks}, i32);
   hipLaunchKernelGGL(seg_block_count_kernel, dim3(blocks), dim3(256), 0, stream,
@@ -167,7 +167,7 @@ std::vector<at::Tensor> bpe_count_async(at::Tensor bytes, at::Tensor req_off,
   hipLaunchKernelGGL(seg_flags_kernel, dim3(blocks), dim3(256), 0, stream,
                      bytes.data_ptr<uint8_t>(), n, flags.data_ptr<uint8_t>());
   hipLaunchKernelGGL(seg_force_starts_kernel, dim3((n_req + 255) / 256), dim3(256), 0,
-                     stream, req_off.data_ptr<int64_t>(), n_req,
+                     stream, req_off.data_ptr<int64_t>(), n_req, n,
                      flags.data_ptr<uint8_t>());
   at::Tensor blk_counts = at::empty({blocks}, i32);
   hipLaunchKernelGGL(seg_block_count_kernel, dim3(blocks), dim3(256), 0, stream,

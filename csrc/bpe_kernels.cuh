@@ -36,10 +36,16 @@ __global__ void seg_flags_kernel(const uint8_t* __restrict__ bytes, int n,
   flags[i] = f;
 }
 
+// A request that starts at or past byte n is empty (a trailing empty text
+// has req_off == n) and forces no start: same `off < n` guard as
+// bpe_ref.segment_starts, and flags[] holds only n bytes.
 __global__ void seg_force_starts_kernel(const int64_t* __restrict__ req_off,
-                                        int n_req, uint8_t* __restrict__ flags) {
+                                        int n_req, int n,
+                                        uint8_t* __restrict__ flags) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n_req) flags[req_off[i]] = 1;
+  if (i >= n_req) return;
+  long long off = req_off[i];
+  if (off >= 0 && off < n) flags[off] = 1;
 }
 
 // per-256-byte-block flag counts (for the ordered compaction scan)

@@ -451,14 +451,17 @@ __global__ void kv_scorer_kernel(const float* __restrict__ stats,  // R x 4
   int lane = threadIdx.x & 63;
   bool ok = lane < n_rep;
   float kv_used = ok ? stats[lane * 4 + 0] : 0.f;
-  float kv_total = ok ? fmaxf(stats[lane * 4 + 1], 1.f) : 1.f;
+  // capacity as reported decides overflow; only the occupancy fraction's
+  // divisor is clamped (a zero-capacity replica overflows on any request)
+  float kv_cap = ok ? stats[lane * 4 + 1] : 1.f;
+  float kv_total = fmaxf(kv_cap, 1.f);
   float queue = ok ? stats[lane * 4 + 2] : 0.f;
   float active = ok ? stats[lane * 4 + 3] : 0.f;
   for (int i = 0; i < n_req; ++i) {
     float p = pred_tokens[i];
     float score = ok ? (w_kv * (1.f - (kv_used + p) / kv_total) - w_q * queue - w_a * active)
                      : -1e30f;
-    if (ok && kv_used + p > kv_total) score -= 1e6f;  // avoid overflowing a replica
+    if (ok && kv_used + p > kv_cap) score -= 1e6f;  // avoid overflowing a replica
     // wave argmax
     float best = score;
     int best_lane = lane;
