@@ -323,38 +323,40 @@ class GpuAdmissionDirect {
     HIP_OK(hipMemcpyAsync(b.d_off, b.h_off, sizeof(int64_t) * (size_t)n_req,
                           hipMemcpyHostToDevice, st));
     int blocks = (int)((n + 255) / 256);
-    hipLaunchKernelGGL(seg_flags_kernel, dim3(blocks), dim3(256), 0, st,
-                       b.d_bytes, (int)n, b.d_flags);
-    hipLaunchKernelGGL(seg_force_starts_kernel, dim3((n_req + 255) / 256),
-                       dim3(256), 0, st, b.d_off, n_req, (int)n, b.d_flags);
-    hipLaunchKernelGGL(seg_block_count_kernel, dim3(blocks), dim3(256), 0,
-                       st, b.d_flags, (int)n, b.d_blk);
+    // fused front end: class-rule flags + forced request starts + block
+    // counts in one pass; it also zeroes d_counts for the BPE kernel
+    hipLaunchKernelGGL(seg_flags_count_kernel, dim3(blocks), dim3(256), 0, st,
+                       b.d_bytes, (int)n, b.d_off, n_req, b.d_flags, b.d_blk,
+                       b.d_counts);
     hipLaunchKernelGGL(excl_scan_kernel, dim3(1), dim3(256), 0, st,
                        b.d_blk, blocks, b.d_excl, b.d_totals);
     hipLaunchKernelGGL(seg_write_kernel, dim3(blocks), dim3(256), 0, st,
                        b.d_flags, (int)n, b.d_excl, b.d_off, n_req,
                        b.d_seg_start, b.d_seg_req);
-    // groups (device-bounded; gflags beyond n_segs cleared so counts stay 0)
-    HIP_OK(hipMemsetAsync(b.d_gflags, 0, n, st));
-    hipLaunchKernelGGL(group_head_flags_dev_kernel, dim3(blocks), dim3(256), 0,
+    // groups (device-bounded; every gflags[i < n] is written, 0 beyond
+    // n_segs, so the buffer needs no clearing)
+    hipLaunchKernelGGL(group_flags_count_kernel, dim3(blocks), dim3(256), 0,
                        st, b.d_seg_start, b.d_seg_req, b.d_totals, b.d_off,
-                       b.d_gflags);
-    hipLaunchKernelGGL(seg_block_count_kernel, dim3(blocks), dim3(256), 0,
-                       st, b.d_gflags, (int)n, b.d_blk);
+                       (int)n, b.d_gflags, b.d_blk);
     hipLaunchKernelGGL(excl_scan_kernel, dim3(1), dim3(256), 0, st,
                        b.d_blk, blocks, b.d_excl, b.d_totals + 1);
     hipLaunchKernelGGL(flag_compact_write_kernel, dim3(blocks), dim3(256), 0,
                        st, b.d_gflags, (int)n, b.d_excl, b.d_ghead);
-    HIP_OK(hipMemsetAsync(b.d_counts, 0, sizeof(int32_t) * n_req, st));
     bool want_cache = pending_slots != nullptr && cache_on_;
     // the cache pipeline finds tokens by out_ids >= 0: merged-away byte
     // positions must read -1, not whatever the previous batch left there
     if (want_cache)
       HIP_OK(hipMemsetAsync(b.d_out_ids, 0xFF, sizeof(int32_t) * n, st));
     long long group_bound = (long long)n / 32 + n_req + 1;
-    int blocks2 = (int)((group_bound + 3) / 4);
-    hipLaunchKernelGGL(bpe_encode_grouped_dev_kernel, dim3(blocks2), dim3(256),
-                       0, st, b.d_bytes, b.d_seg_start, b.d_seg_req,
+    // 8 groups per block: the kernel sums a block's token counts per
+    // request before its atomicAdd, and the atomics on the few d_counts
+    // words, not the merge loop, were what set its duration at one per
+    // wave (profiles/admission_cycle.md: 256/512/1024 threads measured)
+    constexpr int kBpeBlock = 512;
+    constexpr int kGroupsPerBlock = kBpeBlock / 64;
+    int blocks2 = (int)((group_bound + kGroupsPerBlock - 1) / kGroupsPerBlock);
+    hipLaunchKernelGGL(bpe_encode_grouped_dev_kernel, dim3(blocks2),
+                       dim3(kBpeBlock), 0, st, b.d_bytes, b.d_seg_start, b.d_seg_req,
                        b.d_totals, (int)n, b.d_ghead, b.d_totals + 1,
                        d_htab_keys_, d_htab_rank_, htab_mask_, b.d_out_ids,
                        b.d_counts);
