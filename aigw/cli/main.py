@@ -79,7 +79,8 @@ async def _run_shard(args, rank: int = 0, world: int = 1) -> None:
             from aigw.gpu.service import RemoteGPUClient
 
             gpu_services = RemoteGPUClient(
-                gpu_socket, enable_cache=args.semantic_cache
+                gpu_socket, enable_cache=args.semantic_cache,
+                cache_scoped=getattr(args, "cache_scope", "value") == "index",
             )
         else:
             from aigw.gpu import GPUServices
@@ -87,6 +88,8 @@ async def _run_shard(args, rank: int = 0, world: int = 1) -> None:
             gpu_services = GPUServices(
                 device=f"cuda:{rank}", enable_cache=args.semantic_cache,
                 cache_index_dtype=getattr(args, "cache_index_dtype", "bf16"),
+                cache_scoped=getattr(args, "cache_scope", "value") == "index",
+                cache_ttl_s=getattr(args, "cache_ttl_s", 0) or None,
             )
             if gpu_socket:
                 from aigw.gpu.service import GPUServiceHost
@@ -227,7 +230,23 @@ async def _run_shard(args, rank: int = 0, world: int = 1) -> None:
         await front_cleanup()
 
 
+def _check_cache_flags(args) -> None:
+    """Startup errors for semantic-cache flag combinations no front serves."""
+    scoped = getattr(args, "cache_scope", "value") == "index"
+    ttl_s = getattr(args, "cache_ttl_s", 0)
+    if ttl_s < 0:
+        raise SystemExit("--semantic-cache-ttl must be >= 0 (0 = never expire)")
+    if args.front == "fast" and args.gpu and args.semantic_cache and (scoped or ttl_s):
+        # the native front's in-process cache has no row tags: it keeps the
+        # post-hoc fingerprint compare and never expires rows
+        raise SystemExit(
+            "--semantic-cache-scope index and --semantic-cache-ttl are not "
+            "supported by the native front (--front fast) yet: its in-process "
+            "cache has no per-row scope or expiry — use --front lean")
+
+
 def cmd_run(args) -> int:
+    _check_cache_flags(args)
     world = int(os.environ.get("WORLD_SIZE", args.shards))
     rank = int(os.environ.get("RANK", 0))
     if args.workers > 1:
@@ -350,6 +369,16 @@ def main(argv=None) -> int:
     runp.add_argument("--cache-index-dtype", choices=["bf16", "fp8"],
                       default="bf16", dest="cache_index_dtype",
                       help="semantic-cache index precision (fp8 = 2x rows per GB, faster lookups, ~1%% cosine error)")
+    runp.add_argument("--semantic-cache-scope", choices=["value", "index"],
+                      default="value", dest="cache_scope",
+                      help="where a cached answer's scope (model, route, sampling "
+                           "params, credential) is enforced: value = tag compare "
+                           "on the best row only; index = also filter rows by "
+                           "scope inside the lookup kernel, so scopes that store "
+                           "the same prompt each hit their own row")
+    runp.add_argument("--semantic-cache-ttl", type=float, default=0.0,
+                      dest="cache_ttl_s", metavar="SECONDS",
+                      help="expire cached rows after SECONDS (0 = never)")
     runp.set_defaults(fn=cmd_run)
 
     tr = sub.add_parser("translate", help="CRD bundle -> filter config YAML")

@@ -183,6 +183,10 @@ class FastFront:
         self.port = None
 
     async def start(self, host: str, port: int) -> int:
+        # every relayed request reaches the fallback app from loopback, so
+        # its loopback-only cache invalidation cannot tell an operator from
+        # a remote client: off behind this front
+        self.py_server.cache_invalidate_endpoint = False
         app = self.py_server.make_app()
         self._fallback_runner = web.AppRunner(app, access_log=None)
         await self._fallback_runner.setup()

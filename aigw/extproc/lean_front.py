@@ -33,7 +33,7 @@ _GET_ROUTES = {"/v1/models", "/anthropic/v1/models", "/health", "/metrics", "/de
 
 class _Shim:
     """Duck-typed stand-in for aiohttp's request in the simple GET/admin
-    handlers (they use .headers.get, .host, .remote, .json())."""
+    handlers (they use .headers.get, .host, .remote, .json(), .read())."""
 
     __slots__ = ("headers", "host", "remote", "_body")
 
@@ -45,6 +45,9 @@ class _Shim:
 
     async def json(self):
         return json.loads(self._body or b"{}")
+
+    async def read(self):
+        return self._body or b""
 
 
 class _LeanStreamWriter:
@@ -274,7 +277,8 @@ class LeanFront(asyncio.Protocol):
         if root:
             if path.startswith(root + "/"):
                 path = path[len(root):]
-            elif path not in ("/health", "/metrics", "/debug/tasks"):
+            elif path not in ("/health", "/metrics", "/debug/tasks",
+                              "/debug/cache/invalidate"):
                 # admin endpoints stay unprefixed; everything else must
                 # carry the root prefix (mainlib --rootPrefix semantics)
                 self._write_simple(
@@ -310,6 +314,12 @@ class LeanFront(asyncio.Protocol):
                 self._emit(await server._handle_anthropic_models(shim))
             else:
                 self._emit(await server._handle_debug_tasks(shim))
+            return
+        if method == "POST" and path == "/debug/cache/invalidate":
+            # served here, not by the loopback fallback: the handler's
+            # loopback-only guard must see the real peer
+            shim = _Shim(headers, headers.get("host", ""), self._peer, body)
+            self._emit(await server._handle_cache_invalidate(shim))
             return
         if method == "POST" and path == "/v1/gateway/tokenize" and server.gpu is not None:
             shim = _Shim(headers, headers.get("host", ""), self._peer, body)
@@ -361,6 +371,11 @@ async def serve_lean(server: GatewayServer, host: str, port: int,
     fallback_runner = None
     fallback_client = None
     if with_fallback:
+        # the lean front serves /debug/cache/invalidate itself, with the
+        # real peer; the loopback app must not, or any other spelling of
+        # the target (a query, a percent-escape) would reach it relayed
+        # from 127.0.0.1 and pass its loopback-only guard
+        server.cache_invalidate_endpoint = False
         app = server.make_app()
         fallback_runner = web.AppRunner(app, access_log=None)
         await fallback_runner.setup()

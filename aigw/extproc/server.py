@@ -284,6 +284,11 @@ class GatewayServer:
             self.span_recorder = None
         self.max_body_bytes = max_body_bytes
         self.strict_schema = strict_schema
+        # make_app() registers POST /debug/cache/invalidate only while this
+        # is set. A front that relays requests to the app over loopback
+        # clears it first: behind the relay the handler's loopback-only
+        # guard sees 127.0.0.1 for every client.
+        self.cache_invalidate_endpoint = True
         self._session = None  # lean upstream client (aigw.extproc.upstream_client)
         self._started_at = time.time()
         # graceful drain (the Envoy drain-sequence analogue): when
@@ -416,6 +421,8 @@ class GatewayServer:
         app.router.add_get("/health", self._handle_health)
         app.router.add_get("/metrics", self._handle_metrics)
         app.router.add_get("/debug/tasks", self._handle_debug_tasks)
+        if self.cache_invalidate_endpoint:
+            app.router.add_post("/debug/cache/invalidate", self._handle_cache_invalidate)
         if self.gpu is not None:
             app.router.add_post("/v1/gateway/tokenize", self._handle_gpu_tokenize)
         mcp_cfg = self.runtime.config.mcp
@@ -494,6 +501,36 @@ class GatewayServer:
                 }
             )
         return web.json_response({"tasks": tasks, "count": len(tasks)})
+
+    def _cache_scope_kw(self, cache_tag: bytes) -> dict:
+        """scope= for the GPU facade's cache calls, only where it takes one."""
+        if getattr(self.gpu, "cache_scoped", False):
+            return {"scope": cache_tag}
+        return {}
+
+    async def _handle_cache_invalidate(self, request: web.Request) -> web.Response:
+        """Expire semantic-cache rows: all of them, or with a JSON body
+        {"scope": "<hex of a scope tag>"} (mode byte + _cache_fingerprint)
+        the rows of that scope. Guarded like /debug/tasks."""
+        import os as _os
+
+        if _os.environ.get("AIGW_DISABLE_DEBUG") or request.remote not in (
+            "127.0.0.1",
+            "::1",
+        ):
+            return web.Response(status=403)
+        invalidate = getattr(self.gpu, "cache_invalidate", None)
+        if invalidate is None or not self.gpu.cache_enabled:
+            return _json_error(404, "semantic cache is not enabled", "not_found")
+        scope = None
+        raw = await request.read()
+        if raw.strip():
+            try:
+                scope_hex = json.loads(raw).get("scope")
+                scope = bytes.fromhex(scope_hex) if scope_hex is not None else None
+            except (ValueError, TypeError, AttributeError):
+                return _json_error(400, 'body must be {"scope": "<hex>"} or empty')
+        return web.json_response({"invalidated": await invalidate(scope)})
 
     async def _handle_models(self, request: web.Request) -> web.Response:
         rt = self.runtime
@@ -655,7 +692,13 @@ class GatewayServer:
             cache_tag = (b"S" if stream else b"U") + _cache_fingerprint(
                 model, route.route.name, body, request.headers
             )
-            hit, cache_key_vec = await self.gpu.cache_lookup_text(chat_text or b" ")
+            # A GPU facade that advertises cache_scoped also filters index
+            # rows by the tag, so two scopes storing the same prompt each
+            # find their own row; the value-tag compare below stays either
+            # way (a scope-id collision then costs a miss, never a leak).
+            hit, cache_key_vec = await self.gpu.cache_lookup_text(
+                chat_text or b" ", **self._cache_scope_kw(cache_tag)
+            )
             if hit is not None and hit[: len(cache_tag)] == cache_tag:
                 self.metrics._child(self.metrics.cache_events, ("hit",)).inc()
                 body_bytes = hit[len(cache_tag):]
@@ -1046,7 +1089,8 @@ class GatewayServer:
             # same 2 MiB cap as streamed transcripts: 64k slots x unbounded
             # bodies would otherwise grow host memory without limit
         ):
-            await self.gpu.cache_insert(cache_key_vec, cache_tag + rtl.body)
+            await self.gpu.cache_insert(cache_key_vec, cache_tag + rtl.body,
+                                        **self._cache_scope_kw(cache_tag))
         return resp
 
     async def _stream_response(
@@ -1108,7 +1152,8 @@ class GatewayServer:
                 and upstream.status == 200
                 and len(transcript) < (2 << 20)
             ):
-                await self.gpu.cache_insert(cache_key_vec, cache_tag + bytes(transcript))
+                await self.gpu.cache_insert(cache_key_vec, cache_tag + bytes(transcript),
+                                            **self._cache_scope_kw(cache_tag))
         except (UpstreamError, ValueError) as e:
             # mid-stream failure (idle timeout, or malformed provider bytes
             # the translator/codec rejects): the response has started, so

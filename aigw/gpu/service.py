@@ -14,9 +14,13 @@ Wire protocol: 4-byte little-endian length + msgpack map. Ops:
   {id, op:"lookup_batch", texts:[bytes]}          -> {id, hits:[bytes|nil],
                                                       handles:[int|nil]}
   {id, op:"insert", handle:int, response:bytes}   -> {id, ok:true}
+  {id, op:"invalidate"}                           -> {id, rows:int}
   {id, op:"tokenize", text:bytes}                 -> {id, ids:[int]}
   {id, op:"pick", stats:[[f,f,f,f]], predicted:f} -> {id, index:int}
 Replies may arrive out of order (matched by id).
+Optional fields (index-scoped cache): lookup_batch takes scopes:[bytes|nil]
+aligned with texts; insert takes scope:bytes and ttl_s:float; invalidate
+takes scope:bytes. Messages without them behave as before.
 """
 
 from __future__ import annotations
@@ -92,7 +96,12 @@ class GPUServiceHost:
                 # ONE batched submit for the whole RPC (a sequential
                 # per-text await would serialize a micro-batch window per
                 # text)
-                pairs = await self.gpu.lookup_texts_batch(msg["texts"])
+                if msg.get("scopes") is not None:
+                    pairs = await self.gpu.lookup_texts_batch(
+                        msg["texts"], scopes=msg["scopes"]
+                    )
+                else:
+                    pairs = await self.gpu.lookup_texts_batch(msg["texts"])
                 hits, handles = [], []
                 for hit, vec in pairs:
                     hits.append(hit)
@@ -109,8 +118,16 @@ class GPUServiceHost:
             elif op == "insert":
                 vec = self._pending_vecs.pop(msg["handle"], None)
                 if vec is not None:
-                    await self.gpu.cache_insert(vec, msg["response"])
+                    if msg.get("scope") is not None or msg.get("ttl_s") is not None:
+                        await self.gpu.cache_insert(
+                            vec, msg["response"], scope=msg.get("scope"),
+                            ttl_s=msg.get("ttl_s"),
+                        )
+                    else:
+                        await self.gpu.cache_insert(vec, msg["response"])
                 out["ok"] = True
+            elif op == "invalidate":
+                out["rows"] = await self.gpu.cache_invalidate(msg.get("scope"))
             elif op == "tokenize":
                 out["ids"] = await self.gpu.tokenize(msg["text"])
             elif op == "pick":
@@ -134,9 +151,11 @@ class RemoteGPUClient:
     shard's GPU service. Exposes the same interface GatewayServer uses."""
 
     def __init__(self, socket_path: str, *, enable_cache: bool = False,
+                 cache_scoped: bool = False,
                  window_ms: float = 0.1, max_batch: int = 128):
         self.socket_path = socket_path
         self.cache_enabled = enable_cache
+        self.cache_scoped = cache_scoped  # as on the GPUServices behind the socket
         self.window_ms = window_ms
         self.max_batch = max_batch
         self._reader = None
@@ -145,7 +164,7 @@ class RemoteGPUClient:
         self._ids = itertools.count(1)
         self._waiters: dict[int, asyncio.Future] = {}
         self._count_queue: list = []  # (text, future)
-        self._lookup_queue: list = []  # (text, future)
+        self._lookup_queue: list = []  # (text, future, scope)
         self._flush_handle = None
         self._lock = asyncio.Lock()
 
@@ -222,15 +241,16 @@ class RemoteGPUClient:
 
     async def _flush_lookups(self, batch):
         try:
-            reply = await self._call(
-                {"op": "lookup_batch", "texts": [t for t, _ in batch]}
-            )
+            msg = {"op": "lookup_batch", "texts": [t for t, _f, _s in batch]}
+            if any(s is not None for _t, _f, s in batch):
+                msg["scopes"] = [s for _t, _f, s in batch]
+            reply = await self._call(msg)
         except Exception as e:
-            for _t, fut in batch:
+            for _t, fut, _s in batch:
                 if not fut.done():
                     fut.set_exception(e)
             return
-        for (_t, fut), hit, handle in zip(batch, reply["hits"], reply["handles"]):
+        for (_t, fut, _s), hit, handle in zip(batch, reply["hits"], reply["handles"]):
             if not fut.done():
                 fut.set_result((hit, handle))
 
@@ -247,17 +267,28 @@ class RemoteGPUClient:
 
         return await self.count_text_tokens(extract_chat_text(body))
 
-    async def cache_lookup_text(self, text: bytes):
+    async def cache_lookup_text(self, text: bytes, scope=None):
         fut = asyncio.get_running_loop().create_future()
-        self._lookup_queue.append((text or b" ", fut))
+        self._lookup_queue.append((text or b" ", fut, scope))
         self._schedule_flush()
         hit, handle = await fut
         return hit, handle  # handle plays the query-vec role for insert
 
-    async def cache_insert(self, handle, response: bytes) -> None:
+    async def cache_insert(self, handle, response: bytes, scope=None, ttl_s=None) -> None:
         if handle is None:
             return
-        await self._call({"op": "insert", "handle": handle, "response": response})
+        msg = {"op": "insert", "handle": handle, "response": response}
+        if scope is not None:
+            msg["scope"] = scope
+        if ttl_s is not None:
+            msg["ttl_s"] = ttl_s
+        await self._call(msg)
+
+    async def cache_invalidate(self, scope=None) -> int:
+        msg = {"op": "invalidate"}
+        if scope is not None:
+            msg["scope"] = scope
+        return (await self._call(msg))["rows"]
 
     async def tokenize(self, text) -> list[int]:
         if isinstance(text, str):

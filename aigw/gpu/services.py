@@ -39,6 +39,18 @@ def extract_chat_text(body: dict) -> bytes:
     return "\n".join(parts).encode("utf-8", "replace")[:262144] or b" "
 
 
+def _scope_id(scope) -> int:
+    """Index scope id of a caller's scope: None is the wildcard 0, bytes
+    (a scope tag) hash through SemanticCache.scope_id, ints pass."""
+    if scope is None:
+        return 0
+    if isinstance(scope, int):
+        return scope
+    from aigw.ops.semcache import scope_id
+
+    return scope_id(bytes(scope))
+
+
 @dataclass
 class _Pending:
     """One queued work item: a BATCH of texts sharing a future (single
@@ -47,6 +59,7 @@ class _Pending:
 
     texts: list
     want_vec: bool
+    scopes: Optional[list] = None  # cache scope id per text (0 = any scope)
     future: asyncio.Future = None  # type: ignore[assignment]
 
 
@@ -60,6 +73,8 @@ class GPUServices:
         cache_capacity: int = 65536,
         cache_threshold: float = 0.92,
         cache_index_dtype: str = "bf16",  # "bf16" | "fp8" (2x rows/GB, faster lookups)
+        cache_scoped: bool = False,  # filter cache rows by scope in the index
+        cache_ttl_s: Optional[float] = None,  # None: cached rows never expire
         window_ms: float = 0.1,
         max_batch: int = 128,
     ):
@@ -75,10 +90,15 @@ class GPUServices:
                 threshold=cache_threshold,
                 device=device,
                 index_dtype=cache_index_dtype,
+                scoped=cache_scoped,
+                default_ttl_s=cache_ttl_s,
             )
             if enable_cache
             else None
         )
+        # advertised to GatewayServer: when set it passes each request's
+        # scope tag to lookup and insert
+        self.cache_scoped = cache_scoped
         self.window_ms = window_ms
         self.max_batch = max_batch
         import os as _os
@@ -101,9 +121,10 @@ class GPUServices:
 
     # ---- batching core -------------------------------------------------------
 
-    async def _submit_batch(self, texts: list, want_vec: bool):
+    async def _submit_batch(self, texts: list, want_vec: bool, scopes=None):
         loop = asyncio.get_running_loop()
-        item = _Pending(texts=texts, want_vec=want_vec, future=loop.create_future())
+        item = _Pending(texts=texts, want_vec=want_vec, scopes=scopes,
+                        future=loop.create_future())
         self._pending.append(item)
         self._pending_texts += len(texts)
         if self._pending_texts >= self.max_batch:
@@ -117,8 +138,9 @@ class GPUServices:
             )
         return await item.future
 
-    async def _submit(self, text: bytes, want_vec: bool):
-        out = await self._submit_batch([text], want_vec)
+    async def _submit(self, text: bytes, want_vec: bool, scope=None):
+        scopes = None if scope is None else [_scope_id(scope)]
+        out = await self._submit_batch([text], want_vec, scopes)
         return out[0]  # (count, vec, cached_value)
 
     async def _flush(self):
@@ -190,7 +212,15 @@ class GPUServices:
         hits = None
         if any(it.want_vec for it in batch) and self.cache is not None:
             qvecs = self.cache.embed(state["out_ids"], state["req_off"])
-            found = self.cache.lookup(qvecs)  # one fused kernel, all queries
+            scopes = None
+            if any(it.scopes is not None for it in batch):
+                # unscoped items ride the same lookup as wildcards
+                scopes = []
+                for it in batch:
+                    scopes.extend(it.scopes if it.scopes is not None
+                                  else [0] * len(it.texts))
+            # one fused kernel, all queries
+            found = self.cache.lookup(qvecs, scopes=scopes)
             hits = [self.cache.get(h[0]) if h is not None else None for h in found]
         results = []
         for it, (lo, hi) in zip(batch, spans):
@@ -218,17 +248,25 @@ class GPUServices:
         results = await self._submit_batch([t or b" " for t in texts], want_vec=False)
         return [r[0] for r in results]
 
-    async def cache_lookup_text(self, text: bytes):
+    async def cache_lookup_text(self, text: bytes, scope=None):
         """Like cache_lookup but takes pre-extracted text (from the C++
         scanner) instead of a parsed body. Lookup is part of the batched
-        flush — no per-request kernel launches."""
-        _, vec, hit = await self._submit(text or b" ", want_vec=True)
+        flush — no per-request kernel launches. ``scope`` (a tag's bytes or
+        an id) restricts the lookup to that scope's rows."""
+        _, vec, hit = await self._submit(text or b" ", want_vec=True, scope=scope)
         return hit, vec
 
-    async def lookup_texts_batch(self, texts: list[bytes]):
+    async def lookup_texts_batch(self, texts: list[bytes], scopes=None):
         """Batch entry for the shard GPU service: one future per worker
-        batch; returns [(hit_or_None, vec)] aligned with texts."""
-        results = await self._submit_batch([t or b" " for t in texts], want_vec=True)
+        batch; returns [(hit_or_None, vec)] aligned with texts. ``scopes``
+        holds one scope (bytes, id or None) per text."""
+        if scopes is not None:
+            if len(scopes) != len(texts):
+                raise ValueError("scopes must align with texts")
+            scopes = [_scope_id(s) for s in scopes]
+        results = await self._submit_batch(
+            [t or b" " for t in texts], want_vec=True, scopes=scopes
+        )
         return [(hit, vec) for _c, vec, hit in results]
 
     async def tokenize(self, text) -> list[int]:
@@ -242,16 +280,30 @@ class GPUServices:
 
         return await loop.run_in_executor(self._executor, run)
 
-    async def cache_lookup(self, body: dict):
+    async def cache_lookup(self, body: dict, scope=None):
         """Returns (cached_response_bytes | None, query_vec)."""
-        _, vec, hit = await self._submit(extract_chat_text(body), want_vec=True)
+        _, vec, hit = await self._submit(
+            extract_chat_text(body), want_vec=True, scope=scope
+        )
         return hit, vec
 
-    async def cache_insert(self, vec, response: bytes) -> None:
+    async def cache_insert(self, vec, response: bytes, scope=None, ttl_s=None) -> None:
         if vec is None or self.cache is None:
             return
         loop = asyncio.get_running_loop()
-        await loop.run_in_executor(self._executor, self.cache.insert, vec, response)
+        await loop.run_in_executor(
+            self._executor, self.cache.insert, vec, response, _scope_id(scope), ttl_s
+        )
+
+    async def cache_invalidate(self, scope=None) -> int:
+        """Expire the cached rows of one scope (all rows for None)."""
+        if self.cache is None:
+            return 0
+        loop = asyncio.get_running_loop()
+        return await loop.run_in_executor(
+            self._executor, self.cache.invalidate,
+            None if scope is None else _scope_id(scope),
+        )
 
     async def pick_endpoint(self, stats_rows: list[list[float]], predicted: float) -> int:
         """One KV-occupancy scoring call for a single request: returns the

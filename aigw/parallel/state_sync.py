@@ -25,6 +25,7 @@ from __future__ import annotations
 
 import asyncio
 import logging
+import struct
 from typing import Optional
 
 import torch
@@ -33,6 +34,9 @@ import torch.distributed as dist
 from aigw.ratelimit.limiter import SLOTS, bucket_slot
 
 logger = logging.getLogger("aigw.parallel")
+
+# tag trailer of a replicated cache row: scope id, remaining TTL (s)
+_ROW_TAG = struct.Struct("<qi")
 
 
 class StateSync:
@@ -106,15 +110,28 @@ class StateSync:
         response body) so every shard serves every shard's hits
         (RCCL all-gather of semantic-cache index updates).
         Collective sequence is fixed per tick, so shards stay aligned:
-        sizes all-gather, then padded vec + payload all-gathers."""
+        sizes all-gather, then padded vec + payload all-gathers.
+
+        A scoped cache (``cache.scoped``; every shard configured alike)
+        also sends each row's tag, or the row could never answer a scoped
+        query on the receiving shard: a 12-byte trailer per payload record,
+        int64 scope id + int32 remaining TTL in seconds (-1 = never). Rows
+        whose TTL has run out by then are dropped, not inserted. Without
+        the attribute the collectives and bytes are unchanged."""
         cache = self.cache
         rank = dist.get_rank(self.group)
         world = dist.get_world_size(self.group)
-        vecs, values = cache.drain_pending(self.MAX_CACHE_ROWS_PER_TICK)
+        scoped = bool(getattr(cache, "scoped", False))
+        if scoped:
+            vecs, values, metas = cache.drain_pending_scoped(self.MAX_CACHE_ROWS_PER_TICK)
+        else:
+            vecs, values = cache.drain_pending(self.MAX_CACHE_ROWS_PER_TICK)
         payload = bytearray()
-        for v in values:
+        for i, v in enumerate(values):
             payload.extend(len(v).to_bytes(4, "little"))
             payload.extend(v)
+            if scoped:
+                payload.extend(_ROW_TAG.pack(*metas[i]))
         sizes = torch.tensor([vecs.shape[0], len(payload)], dtype=torch.int64,
                              device=self.device)
         all_sizes = [torch.zeros_like(sizes) for _ in range(world)]
@@ -148,7 +165,15 @@ class StateSync:
                 off += 4
                 value = blob[off : off + ln]
                 off += ln
-                cache.insert_remote(rows[i], value)
+                if not scoped:
+                    cache.insert_remote(rows[i], value)
+                    continue
+                scope, ttl_s = _ROW_TAG.unpack_from(blob, off)
+                off += _ROW_TAG.size
+                if ttl_s == -1:
+                    cache.insert_remote(rows[i], value, scope=scope, ttl_s=None)
+                elif ttl_s > 0:
+                    cache.insert_remote(rows[i], value, scope=scope, ttl_s=ttl_s)
 
     # ---- background loop -----------------------------------------------------
 

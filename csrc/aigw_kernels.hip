@@ -397,6 +397,100 @@ std::vector<at::Tensor> cache_topk(at::Tensor index, at::Tensor q) {
   return {hi, idx};
 }
 
+// cache_topk with the per-row (scope, expiry) filter of
+// cache_topk_scoped_kernel_t: a query sees row r only if
+// row_expiry[r] > now and (q_scope == 0 or row_scope[r] == q_scope).
+// idx is -1 and hi is 0 for a query that no row may answer.
+template <class E>
+static void launch_cache_topk_scoped(const at::Tensor& index, const at::Tensor& q,
+                                     const at::Tensor& row_scope,
+                                     const at::Tensor& row_expiry,
+                                     const at::Tensor& q_scope, int now,
+                                     at::Tensor& best) {
+  using elem = typename E::elem;
+  constexpr int ROWTILES = 16;
+  long long n_rows = index.size(0);
+  int n_q = (int)q.size(0), dim = (int)q.size(1);
+  long long blocks = (n_rows + 64 * ROWTILES - 1) / (64 * ROWTILES);
+  auto* ip = reinterpret_cast<const elem*>(index.data_ptr());
+  auto* q_base = reinterpret_cast<const elem*>(q.data_ptr());
+  auto* best_p = reinterpret_cast<unsigned long long*>(best.data_ptr<int64_t>());
+  auto* rs = reinterpret_cast<const long long*>(row_scope.data_ptr<int64_t>());
+  auto* re = row_expiry.data_ptr<int32_t>();
+  auto* qsc = reinterpret_cast<const long long*>(q_scope.data_ptr<int64_t>());
+  // query block + blk_best + q_scope stage
+  size_t lds_bytes = 128 * (size_t)(dim + E::kPad) * sizeof(elem) + 128 * 8 + 128 * 8;
+  auto launch = [&](auto kernel, int q0) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), lds_bytes,
+                       current_stream(), ip, n_rows, q_base + (long long)q0 * dim,
+                       std::min(128, n_q - q0), dim, best_p + q0, rs, re, qsc + q0, now);
+  };
+  for (int q0 = 0; q0 < n_q; q0 += 128) {
+    switch (dim >> 5) {
+      case 12: launch(&cache_topk_scoped_kernel_t<E, 12, ROWTILES>, q0); break;
+      case 8: launch(&cache_topk_scoped_kernel_t<E, 8, ROWTILES>, q0); break;
+      case 16: launch(&cache_topk_scoped_kernel_t<E, 16, ROWTILES>, q0); break;
+      case 4: launch(&cache_topk_scoped_kernel_t<E, 4, ROWTILES>, q0); break;
+      default:
+        TORCH_CHECK(false, "cache_topk_scoped: unsupported dim ", dim,
+                    " (supported: 128/256/384/512)");
+    }
+  }
+}
+
+std::vector<at::Tensor> cache_topk_scoped(at::Tensor index, at::Tensor q,
+                                          at::Tensor row_scope, at::Tensor row_expiry,
+                                          at::Tensor q_scope, int64_t now) {
+  check_cuda(index, "index");
+  check_cuda(q, "q");
+  check_cuda(row_scope, "row_scope");
+  check_cuda(row_expiry, "row_expiry");
+  check_cuda(q_scope, "q_scope");
+  bool fp8 = index.scalar_type() == at::kFloat8_e4m3fn;
+  TORCH_CHECK(index.scalar_type() == q.scalar_type(), "index/q dtype mismatch");
+  TORCH_CHECK(fp8 || index.scalar_type() == at::kBFloat16,
+              "bf16 or float8_e4m3fn required");
+  TORCH_CHECK(index.dim() == 2 && q.dim() == 2, "index and q must be 2-D");
+  long long n_rows = index.size(0);
+  int n_q = (int)q.size(0), dim = (int)q.size(1);
+  TORCH_CHECK(index.size(1) == dim, "dim mismatch");
+  TORCH_CHECK(dim % 32 == 0 && dim <= 512, "dim must be a multiple of 32, <= 512");
+  TORCH_CHECK(n_q <= 256, "cache_topk_scoped: at most 256 queries per call");
+  TORCH_CHECK(row_scope.scalar_type() == at::kLong && row_scope.dim() == 1 &&
+                  row_scope.size(0) == n_rows,
+              "row_scope must be int64[n_rows]");
+  TORCH_CHECK(row_expiry.scalar_type() == at::kInt && row_expiry.dim() == 1 &&
+                  row_expiry.size(0) == n_rows,
+              "row_expiry must be int32[n_rows]");
+  TORCH_CHECK(q_scope.scalar_type() == at::kLong && q_scope.dim() == 1 &&
+                  q_scope.size(0) == n_q,
+              "q_scope must be int64[n_q]");
+  TORCH_CHECK(row_scope.device() == index.device() &&
+                  row_expiry.device() == index.device() &&
+                  q_scope.device() == index.device() && q.device() == index.device(),
+              "cache_topk_scoped: all tensors must be on one device");
+  // the kernel reads a lane's 4 row tags as 16-byte vectors
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(row_scope.data_ptr()) % 32 == 0 &&
+                  reinterpret_cast<uintptr_t>(row_expiry.data_ptr()) % 16 == 0,
+              "row_scope/row_expiry must start 32/16-byte aligned (row 4k of the "
+              "allocation)");
+  TORCH_CHECK(now >= INT32_MIN && now <= INT32_MAX, "now must fit int32");
+  auto best = at::zeros({n_q}, at::TensorOptions().dtype(at::kLong).device(q.device()));
+  if (n_q == 0 || n_rows == 0)
+    return {best, at::full({n_q}, -1, best.options().dtype(at::kInt))};
+  if (fp8)
+    launch_cache_topk_scoped<CacheElemFp8>(index, q, row_scope, row_expiry, q_scope,
+                                           (int)now, best);
+  else
+    launch_cache_topk_scoped<CacheElemBf16>(index, q, row_scope, row_expiry, q_scope,
+                                            (int)now, best);
+  auto hi = best.bitwise_right_shift(32).to(at::kLong);
+  auto idx = at::where(best == 0, -1, best.bitwise_and(0xFFFFFFFFLL)).to(at::kInt);
+  return {hi, idx};
+}
+
 at::Tensor kv_score_assign(at::Tensor stats, at::Tensor pred_tokens, double w_kv,
                            double w_q, double w_a) {
   check_cuda(stats, "stats");
@@ -448,6 +542,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("relu") = false);
   m.def("l2norm_rows", &l2norm_rows, "row-wise L2 normalize fp32->bf16");
   m.def("cache_topk", &cache_topk, "fused cosine-sim argmax over cache index");
+  m.def("cache_topk_scoped", &cache_topk_scoped,
+        "cache_topk over the rows a query may see: row r answers query j iff "
+        "row_expiry[r] > now and (q_scope[j] == 0 or row_scope[r] == q_scope[j]). "
+        "Returns (hi, idx); idx -1 / hi 0 where no row is eligible. Unlike "
+        "cache_topk, row_scope must start 32-byte and row_expiry 16-byte "
+        "aligned (the kernel reads 4 row tags as 16-byte vectors): pass "
+        "tensors sliced from row 4k of their allocation, not e.g. row_scope[1:].");
   m.def("kv_score_assign", &kv_score_assign, "greedy KV-occupancy assignment");
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
 }

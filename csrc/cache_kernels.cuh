@@ -437,6 +437,197 @@ cache_topk_lds_kernel_t(const bf16* __restrict__ index, long long n_rows,
 }
 
 // ---------------------------------------------------------------------------
+// 3b. Scope- and TTL-filtered variant of the two LDS-staged kernels above.
+//    Every index row carries a tag (scope id, expiry second); row r may
+//    answer query j iff
+//      row_expiry[r] > now && (q_scope[j] == 0 || row_scope[r] == q_scope[j])
+//    and ineligible rows are dropped before anything is reduced: filtering
+//    the argmax afterwards cannot bring back the eligible row it discarded.
+//    One template over the element type; the unfiltered kernels stay as
+//    they are (sibling, not a flag, so their code does not move). Same
+//    structure: query block in LDS, A-tile ping-pong, ks-outer MFMAs.
+// ---------------------------------------------------------------------------
+
+struct CacheElemBf16 {
+  using elem = bf16;
+  using frag = short8;  // 8 bf16 per lane per k-step
+  static constexpr int kPad = 8;  // row pad in elements, see the kernels above
+  static __device__ __forceinline__ frag zero() { return frag{0, 0, 0, 0, 0, 0, 0, 0}; }
+  static __device__ __forceinline__ floatx4 mfma(frag a, frag b, floatx4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+  }
+};
+
+struct CacheElemFp8 {
+  using elem = uint8_t;
+  using frag = long;  // 8 fp8 per lane per k-step
+  static constexpr int kPad = 16;
+  static __device__ __forceinline__ frag zero() { return 0L; }
+  static __device__ __forceinline__ floatx4 mfma(frag a, frag b, floatx4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a, b, c, 0, 0, 0);
+  }
+};
+
+// Tags of the lane's four index rows (i0 + kgrp*4 + r in the MFMA result
+// layout). Loaded raw in load_tile, next to the A-tile loads of the
+// ping-pong and behind the same wait, and compared only in compute_tile.
+// What the mask costs and why: profiles/cache_topk_scoped.md.
+struct RowTags {
+  long long scope[4];
+  int expiry[4];
+};
+
+// g0 = first of the lane's 4 rows, a multiple of 4. A full group is two
+// 16-byte scope loads and one 16-byte expiry load (the 16 lanes of a kgrp
+// share the address); the group that straddles n_rows is read row by row
+// and never past the end. Needs row_scope 32-byte and row_expiry 16-byte
+// aligned (the host wrapper checks). Per-row loads at clamped indices
+// instead (no branch) measured within 2% of this either way.
+__device__ __forceinline__ void load_row_tags(RowTags& tg,
+                                              const long long* __restrict__ row_scope,
+                                              const int* __restrict__ row_expiry,
+                                              long long g0, long long n_rows) {
+  if (g0 + 4 <= n_rows) {
+    typedef __attribute__((ext_vector_type(2))) long long ll2;
+    typedef __attribute__((ext_vector_type(4))) int int4v;
+    ll2 s01 = *reinterpret_cast<const ll2*>(&row_scope[g0]);
+    ll2 s23 = *reinterpret_cast<const ll2*>(&row_scope[g0 + 2]);
+    int4v e = *reinterpret_cast<const int4v*>(&row_expiry[g0]);
+    tg.scope[0] = s01[0];
+    tg.scope[1] = s01[1];
+    tg.scope[2] = s23[0];
+    tg.scope[3] = s23[1];
+    #pragma unroll
+    for (int r = 0; r < 4; ++r) tg.expiry[r] = e[r];
+  } else {
+    #pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      bool ok = g0 + r < n_rows;
+      tg.scope[r] = ok ? row_scope[g0 + r] : 0;
+      tg.expiry[r] = ok ? row_expiry[g0 + r] : INT_MIN;
+    }
+  }
+}
+
+// Dynamic LDS: 128 * (KSTEPS*32 + kPad) * sizeof(elem) query block, then
+// 128 * 8 blk_best, then 128 * 8 q_scope.
+template <class E, int KSTEPS, int ROWTILES>
+__global__ void __launch_bounds__(256)
+cache_topk_scoped_kernel_t(const typename E::elem* __restrict__ index, long long n_rows,
+                           const typename E::elem* __restrict__ q, int n_q /* <= 128 */,
+                           int dim, unsigned long long* __restrict__ best,
+                           const long long* __restrict__ row_scope,
+                           const int* __restrict__ row_expiry,
+                           const long long* __restrict__ q_scope, int now) {
+  using elem = typename E::elem;
+  using frag_t = typename E::frag;
+  constexpr int DIMP = KSTEPS * 32 + E::kPad;
+  constexpr int QS_BYTES = 128 * DIMP * (int)sizeof(elem);
+  extern __shared__ unsigned char smem[];
+  elem* qs = reinterpret_cast<elem*>(smem);
+  unsigned long long* blk_best = reinterpret_cast<unsigned long long*>(smem + QS_BYTES);
+  long long* qsc_s = reinterpret_cast<long long*>(smem + QS_BYTES + 128 * 8);
+  if (threadIdx.x < 128) {
+    blk_best[threadIdx.x] = 0;
+    qsc_s[threadIdx.x] = threadIdx.x < (unsigned)n_q ? q_scope[threadIdx.x] : 0;
+  }
+  int chunks_per_row = dim / 8;
+  for (int idx = threadIdx.x; idx < n_q * chunks_per_row; idx += 256) {
+    int r = idx / chunks_per_row, c = (idx - r * chunks_per_row) * 8;
+    *reinterpret_cast<frag_t*>(&qs[r * DIMP + c]) =
+        *reinterpret_cast<const frag_t*>(&q[(long long)r * dim + c]);
+  }
+  __syncthreads();
+  int wave = threadIdx.x >> 6;
+  int lane = threadIdx.x & 63;
+  int row = lane & 15;
+  int kgrp = lane >> 4;
+  auto load_tile = [&](frag_t (&frag)[KSTEPS], RowTags& tg, int t) {
+    long long i0 = ((long long)blockIdx.x * 4 * ROWTILES + wave * ROWTILES + t) * 16;
+    bool i_ok = i0 < n_rows && (i0 + row) < n_rows;
+    #pragma unroll
+    for (int ks = 0; ks < KSTEPS; ++ks) {
+      int kk = ks * 32 + kgrp * 8;
+      if (i_ok)
+        frag[ks] = *reinterpret_cast<const frag_t*>(&index[(i0 + row) * dim + kk]);
+      else
+        frag[ks] = E::zero();
+    }
+    // compute_tile skips a tile with i0 >= n_rows, so its tags stay unread
+    if (i0 < n_rows) load_row_tags(tg, row_scope, row_expiry, i0 + kgrp * 4, n_rows);
+  };
+  constexpr int QT = 8;  // 128 queries / 16
+  auto compute_tile = [&](frag_t (&frag)[KSTEPS], const RowTags& tg, int t) {
+    long long i0 = ((long long)blockIdx.x * 4 * ROWTILES + wave * ROWTILES + t) * 16;
+    if (i0 >= n_rows) return;
+    floatx4 acc[QT];
+    #pragma unroll
+    for (int qt = 0; qt < QT; ++qt) acc[qt] = floatx4{0.f, 0.f, 0.f, 0.f};
+    int qrow = min(row, n_q - 1);  // LDS reads always in-bounds
+    #pragma unroll
+    for (int ks = 0; ks < KSTEPS; ++ks) {
+      int kk = ks * 32 + kgrp * 8;
+      #pragma unroll
+      for (int qt = 0; qt < QT; ++qt) {
+        frag_t b = *reinterpret_cast<const frag_t*>(&qs[(qt * 16 + qrow) * DIMP + kk]);
+        acc[qt] = E::mfma(frag[ks], b, acc[qt]);
+      }
+    }
+    int lim = (int)min((long long)16, n_rows - i0);
+    bool live[4];  // in range and not expired: the query-independent half
+    #pragma unroll
+    for (int r = 0; r < 4; ++r) live[r] = (kgrp * 4 + r < lim) && tg.expiry[r] > now;
+    #pragma unroll
+    for (int qt = 0; qt < QT; ++qt) {
+      int q0 = qt * 16;
+      long long qsc = qsc_s[q0 + row];
+      // Mask per element, before the lane's 4-way max: a foreign or dead
+      // row that out-scores the lane's eligible one must not hide it.
+      // Ties go to the higher row, as pack_score's do across lanes.
+      // (A branch-free select form of this loop measured 17% slower on
+      // the bf16 kernel: profiles/cache_topk_scoped.md.)
+      float best_s = 0.f;
+      int best_r = -1;
+      #pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        bool ok = live[r] && (qsc == 0 || tg.scope[r] == qsc);
+        if (ok && (best_r < 0 || acc[qt][r] >= best_s)) {
+          best_s = acc[qt][r];
+          best_r = r;
+        }
+      }
+      // 0 = nothing eligible (pack_score of a real score is never 0)
+      unsigned long long p = 0;
+      if (best_r >= 0 && (q0 + row) < n_q) {
+        long long irow = i0 + kgrp * 4 + best_r;
+        p = pack_score(best_s, (unsigned)(irow & 0xFFFFFFFF));
+      }
+      #pragma unroll
+      for (int off = 16; off < 64; off <<= 1) {
+        unsigned long long o = shfl_xor_u64(p, off);
+        if (o > p) p = o;
+      }
+      // no eligible row in this tile for the query: no atomic, so a query
+      // nothing may answer keeps the best == 0 sentinel
+      if (kgrp == 0 && p) atomicMax(&blk_best[q0 + row], p);
+    }
+  };
+  frag_t frag_a[KSTEPS], frag_b[KSTEPS];
+  RowTags tag_a, tag_b;
+  load_tile(frag_a, tag_a, 0);
+  static_assert(ROWTILES % 2 == 0, "pipeline assumes even ROWTILES");
+  for (int t = 0; t < ROWTILES; t += 2) {
+    load_tile(frag_b, tag_b, t + 1);
+    compute_tile(frag_a, tag_a, t);
+    if (t + 2 < ROWTILES) load_tile(frag_a, tag_a, t + 2);
+    compute_tile(frag_b, tag_b, t + 1);
+  }
+  __syncthreads();
+  if (threadIdx.x < (unsigned)n_q && blk_best[threadIdx.x])
+    atomicMax(&best[threadIdx.x], blk_best[threadIdx.x]);
+}
+
+// ---------------------------------------------------------------------------
 // 4. KV-occupancy endpoint scorer: greedy sequential assignment of a request
 //    batch to replicas. One wave; lane = replica. score = w_kv*(free KV frac
 //    after assignment) - w_q*queue_depth - w_a*active. Mirrors the EPP

@@ -137,6 +137,32 @@ def main():
         "TFLOPs": round(2 * args.index_rows * args.batch * 384 / dt / 1e12, 2),
     }))
 
+    # scope/TTL-filtered lookup on the same data: 8 scopes, every row live,
+    # every query scoped, so each element pays the full tag compare. The
+    # extra traffic is the 12 B/row tag.
+    row_scope = torch.randint(1, 9, (args.index_rows,), device="cuda")
+    row_expiry = torch.full((args.index_rows,), 0x7FFFFFFF, dtype=torch.int32,
+                            device="cuda")
+    q_scope = torch.randint(1, 9, (args.batch,), device="cuda")
+    for name, idx_t, q_t, elem_bytes in (
+        ("cache_topk_scoped", index, q, 2),
+        ("cache_topk_scoped_fp8", index8, q8, 1),
+    ):
+        unscoped_dt = timeit(lambda: tok.hip.cache_topk(idx_t, q_t))
+        dt = timeit(lambda: tok.hip.cache_topk_scoped(
+            idx_t, q_t, row_scope, row_expiry, q_scope, 1))
+        print(json.dumps({
+            "kernel": name,
+            "rows": args.index_rows,
+            "queries": args.batch,
+            "ms": round(dt * 1e3, 3),
+            "unscoped_ms": round(unscoped_dt * 1e3, 3),
+            "ratio": round(dt / unscoped_dt, 3),
+            "traffic_ratio": round((384 * elem_bytes + 12) / (384 * elem_bytes), 3),
+            "TB_per_s_index_read": round(
+                args.index_rows * (384 * elem_bytes + 12) / dt / 1e12, 3),
+        }))
+
     stats = torch.rand(8, 4, device="cuda")
     stats[:, 1] = 1000
     pred = torch.rand(args.batch, device="cuda") * 100
