@@ -357,6 +357,7 @@ PYBIND11_MODULE(aigw_fast, m) {
            py::call_guard<py::gil_scoped_release>())
       .def("stop", &FastServer::stop, py::call_guard<py::gil_scoped_release>())
       .def("gpu_direct_stats", &FastServer::gpu_direct_stats)
+      .def("gpu_direct_take_us", &FastServer::gpu_direct_take_us)
       .def("rl_collect_deltas", &FastServer::rl_collect_deltas)
       .def("rl_apply_remote", &FastServer::rl_apply_remote)
       .def("rl_local_spent", &FastServer::rl_local_spent)

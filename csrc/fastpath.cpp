@@ -178,6 +178,8 @@ struct HttpHead {
 
 constexpr size_t kMaxHead = 64 * 1024;
 constexpr size_t kMaxBody = 64 * 1024 * 1024;
+// per-connection buffers above this capacity are released after the request
+constexpr size_t kKeepBuf = 1024 * 1024;
 
 // parse a full head present in buf[0..); returns false on malformed
 bool parse_head(const std::string& buf, size_t head_end, bool is_request, HttpHead* out) {
@@ -681,8 +683,8 @@ class DirectGpuBatcher {
 
   ~DirectGpuBatcher() { stop(); }
 
-  int64_t count_text(const std::string& text) {
-    CacheLookup cl = count_lookup_text(text);
+  int64_t count_text(std::string&& text, std::string* reclaim = nullptr) {
+    CacheLookup cl = count_lookup_text(std::move(text), reclaim);
     // the batcher parks a query vector whenever the cache is on; a
     // count-only caller (streamed requests) must return the slot or the
     // 4096-slot pending pool starves after enough streams
@@ -690,9 +692,21 @@ class DirectGpuBatcher {
     return cl.tokens;
   }
 
+  int64_t count_text(const std::string& text) {
+    return count_text(std::string(text));
+  }
+
+  // The waiter owns the request text from enqueue() on, so the queue is
+  // pointers only and pack is the one copy between extraction and H2D.
+  // Ownership of `text`: the batcher thread may read it only between
+  // dequeue and the end of pack; the request thread may touch it only
+  // after it has observed `done` under `m` (collect() hands the buffer
+  // back then). A request thread whose collect() timed out with `done`
+  // still false must not touch it and just drops its reference.
   struct Waiter2 {
     std::mutex m;
     std::condition_variable cv;
+    std::string text;
     bool done = false;
     int64_t count = 0;
     int32_t row = -1;
@@ -713,23 +727,37 @@ class DirectGpuBatcher {
   // response time, hiding the admission batch behind the upstream
   // round-trip (the reference also charges usage post-response:
   // processor_impl.go buildDynamicMetadata runs on response complete).
-  std::shared_ptr<Waiter2> enqueue(const std::string& text) {
+  std::shared_ptr<Waiter2> enqueue(std::string&& text) {
     if (stopping_) return nullptr;
     auto w = std::make_shared<Waiter2>();
+    w->text = std::move(text);
+    size_t n = w->text.size();
     {
       std::lock_guard<std::mutex> lk(mu_);
-      q_texts_.push_back(text);
-      q_waiters_.push_back(w);
+      q_.push_back(w);
+      q_bytes_ += n;
       cv_.notify_one();
     }
     return w;
   }
 
-  CacheLookup collect(const std::shared_ptr<Waiter2>& w) {
+  std::shared_ptr<Waiter2> enqueue(const std::string& text) {
+    return enqueue(std::string(text));
+  }
+
+  // When `reclaim` is given and the batch completed, the text buffer is
+  // swapped back into *reclaim and cleared, so its capacity serves the
+  // caller's next request and the batcher thread frees no strings.
+  CacheLookup collect(const std::shared_ptr<Waiter2>& w,
+                      std::string* reclaim = nullptr) {
     CacheLookup out;
     if (w == nullptr) return out;
     std::unique_lock<std::mutex> lk(w->m);
     w->cv.wait_for(lk, std::chrono::seconds(30), [&] { return w->done; });
+    if (w->done && reclaim != nullptr) {
+      reclaim->swap(w->text);
+      reclaim->clear();
+    }
     out.tokens = w->count;
     out.row = w->row;
     out.score = w->score;
@@ -740,8 +768,13 @@ class DirectGpuBatcher {
   // count + (when the cache is enabled) lookup in ONE GPU batch. The
   // returned slot (if >= 0) must be passed to cache_insert_slot() or
   // cache_release_slot() by the caller exactly once.
+  CacheLookup count_lookup_text(std::string&& text,
+                                std::string* reclaim = nullptr) {
+    return collect(enqueue(std::move(text)), reclaim);
+  }
+
   CacheLookup count_lookup_text(const std::string& text) {
-    return collect(enqueue(text));
+    return collect(enqueue(std::string(text)));
   }
 
   bool init_cache(const uint16_t* emb, int vocab, const uint16_t* proj,
@@ -821,12 +854,16 @@ class DirectGpuBatcher {
            !stats_max_us.compare_exchange_weak(prev, (uint64_t)bt)) {}
     for (int i = 0; i < n; ++i) {
       auto& w = fl.waiters[i];
-      std::lock_guard<std::mutex> lk(w->m);
-      w->count = counts[i];
-      w->row = rows[i];
-      w->score = scores[i];
-      w->slot = fl.slots[i];
-      w->done = true;
+      {
+        std::lock_guard<std::mutex> lk(w->m);
+        w->count = counts[i];
+        w->row = rows[i];
+        w->score = scores[i];
+        w->slot = fl.slots[i];
+        w->done = true;
+      }
+      // notify after unlocking so the woken thread does not block on
+      // w->m straight away; fl.waiters keeps the waiter alive across it
       w->cv.notify_all();
     }
     stats_fulfill_us += (uint64_t)(now_us() - w1);
@@ -838,12 +875,14 @@ class DirectGpuBatcher {
   void loop() {
     std::vector<int64_t> offs;
     int next_set = 0;
+    // empty between batches; its capacity rotates through q_ and the
+    // in-flight sets, so the steady state allocates nothing here
+    std::vector<std::shared_ptr<Waiter2>> waiters;
     while (!stopping_) {
-      std::vector<std::string> texts;
-      std::vector<std::shared_ptr<Waiter2>> waiters;
+      int64_t k0 = now_us();
       {
         std::unique_lock<std::mutex> lk(mu_);
-        if (q_texts_.empty()) {
+        if (q_.empty()) {
           int other = 1 - next_set;
           if (inflight_[other].valid) {
             // nothing queued yet: retire the running batch first (its
@@ -852,19 +891,30 @@ class DirectGpuBatcher {
             finish_set(other);
             continue;
           }
-          cv_.wait(lk, [&] { return stopping_ || !q_texts_.empty(); });
+          cv_.wait(lk, [&] { return stopping_ || !q_.empty(); });
           if (stopping_) break;
+          k0 = now_us();  // take phase starts when work is available
         }
-        size_t take = 0, bytes = 0;
-        while (take < q_texts_.size() && (int)take < max_batch_ &&
-               bytes + q_texts_[take].size() <= max_bytes_)
-          bytes += q_texts_[take++].size();
-        if (take == 0) take = 1;  // oversized single text: truncated below
-        texts.assign(q_texts_.begin(), q_texts_.begin() + take);
-        waiters.assign(q_waiters_.begin(), q_waiters_.begin() + take);
-        q_texts_.erase(q_texts_.begin(), q_texts_.begin() + take);
-        q_waiters_.erase(q_waiters_.begin(), q_waiters_.begin() + take);
+        if (q_.size() <= (size_t)max_batch_ && q_bytes_ <= max_bytes_) {
+          // steady state: the whole queue is the batch — swap it out
+          waiters.swap(q_);
+          q_bytes_ = 0;
+        } else {
+          size_t take = 0, bytes = 0;
+          while (take < q_.size() && (int)take < max_batch_ &&
+                 bytes + q_[take]->text.size() <= max_bytes_)
+            bytes += q_[take++]->text.size();
+          if (take == 0) {  // oversized single text: truncated below
+            take = 1;
+            bytes = q_[0]->text.size();
+          }
+          waiters.assign(std::make_move_iterator(q_.begin()),
+                         std::make_move_iterator(q_.begin() + take));
+          q_.erase(q_.begin(), q_.begin() + take);
+          q_bytes_ -= bytes;
+        }
       }
+      stats_take_us += (uint64_t)(now_us() - k0);
       finish_set(next_set);  // the set must be idle before its staging reuse
       int64_t p0 = now_us();
       // pack straight into the idle set's pinned staging buffer: the
@@ -874,14 +924,15 @@ class DirectGpuBatcher {
       char* stage = admission_staging(adm_, next_set);
       size_t used = 0;
       offs.clear();
-      for (auto& t : texts) {
+      for (auto& w : waiters) {
+        const std::string& t = w->text;
         offs.push_back((int64_t)used);
         size_t room = max_bytes_ - used;
         size_t take_n = std::min(t.size(), room);
         memcpy(stage + used, t.data(), take_n);
         used += take_n;
       }
-      size_t nt = texts.size();
+      size_t nt = waiters.size();
       std::vector<int32_t> slots((size_t)nt, -1);
       if (cache_on_) {
         std::lock_guard<std::mutex> lk(slot_mu_);
@@ -901,15 +952,18 @@ class DirectGpuBatcher {
         if (used > 0) stats_errors++;
         for (size_t i = 0; i < nt; ++i) {
           auto& w = waiters[i];
-          std::lock_guard<std::mutex> lk(w->m);
-          w->slot = slots[i];
-          w->done = true;
+          {
+            std::lock_guard<std::mutex> lk(w->m);
+            w->slot = slots[i];
+            w->done = true;
+          }
           w->cv.notify_all();
         }
+        waiters.clear();
         continue;
       }
       InFlight& fl = inflight_[next_set];
-      fl.waiters = std::move(waiters);
+      fl.waiters.swap(waiters);  // fl.waiters was cleared by finish_set
       fl.slots = std::move(slots);
       fl.t0 = now_us();
       fl.valid = true;
@@ -925,13 +979,15 @@ class DirectGpuBatcher {
     std::vector<std::shared_ptr<Waiter2>> all;
     {
       std::lock_guard<std::mutex> lk(mu_);
-      all = std::move(q_waiters_);
-      q_waiters_.clear();
-      q_texts_.clear();
+      all = std::move(q_);
+      q_.clear();
+      q_bytes_ = 0;
     }
     for (auto& w : all) {
-      std::lock_guard<std::mutex> lk(w->m);
-      w->done = true;
+      {
+        std::lock_guard<std::mutex> lk(w->m);
+        w->done = true;
+      }
       w->cv.notify_all();
     }
   }
@@ -953,6 +1009,8 @@ class DirectGpuBatcher {
   std::atomic<uint64_t> stats_submit_us{0};
   std::atomic<uint64_t> stats_wait_us{0};
   std::atomic<uint64_t> stats_fulfill_us{0};
+  // batcher awake with work available -> end of dequeue, lock wait included
+  std::atomic<uint64_t> stats_take_us{0};
 
  private:
   int max_batch_ = 1024;
@@ -960,8 +1018,8 @@ class DirectGpuBatcher {
   std::atomic<bool> stopping_{false};
   std::mutex mu_;
   std::condition_variable cv_;
-  std::vector<std::string> q_texts_;
-  std::vector<std::shared_ptr<Waiter2>> q_waiters_;
+  std::vector<std::shared_ptr<Waiter2>> q_;  // each waiter owns its text
+  size_t q_bytes_ = 0;                       // sum of queued text sizes
   InFlight inflight_[2];
   std::thread worker_;
 };
@@ -994,6 +1052,7 @@ class ConnHandler {
 
   void run() {
     std::string buf;
+    std::string body;  // capacity survives across requests
     char tmp[65536];
     for (;;) {
       // locate a complete head
@@ -1034,17 +1093,31 @@ class ConnHandler {
         simple_reply(400, "invalid_request_error", "bad content-length", true);
         return;
       }
-      while (buf.size() < req.head_len + (size_t)clen) {
-        ssize_t r = read_some(fd_, tmp, sizeof(tmp));
-        if (r <= 0) return;
-        srv_->stats_.bytes_in += (uint64_t)r;
-        buf.append(tmp, (size_t)r);
+      // body bytes that arrived with the head move into `body`; the rest
+      // is read straight into its tail (no stack bounce, no substr). Bytes
+      // of a pipelined next request that came with this head stay in buf.
+      const size_t need = (size_t)clen;
+      size_t have = std::min(buf.size() - req.head_len, need);
+      body.assign(buf.data() + req.head_len, have);
+      if (req.head_len + have == buf.size())
+        buf.clear();
+      else
+        buf.erase(0, req.head_len + have);
+      if (have < need) {
+        body.resize(need);
+        while (have < need) {
+          ssize_t r = read_some(fd_, &body[have], need - have);
+          if (r <= 0) return;
+          srv_->stats_.bytes_in += (uint64_t)r;
+          have += (size_t)r;
+        }
       }
-      std::string body = buf.substr(req.head_len, (size_t)clen);
-      buf.erase(0, req.head_len + (size_t)clen);
 
       bool keep = handle_request(req, body);
       if (!keep) return;
+      // one huge request must not pin its buffers for the connection's life
+      if (body.capacity() > kKeepBuf) std::string().swap(body);
+      if (text_buf_.capacity() > kKeepBuf) std::string().swap(text_buf_);
     }
   }
 
@@ -1064,6 +1137,21 @@ class ConnHandler {
     // one-pass native scan: model + stream + chat text + model span
     aigw_core::Scan sc{body.data(), body.data() + body.size()};
     sc.base = body.data();
+    // collect the chat text into the connection's recycled buffer; it
+    // comes back (emptied, capacity kept) from collect() after admission,
+    // or from this guard when the request never reaches admission
+    text_buf_.clear();
+    sc.text.swap(text_buf_);
+    struct TextReturn {
+      std::string& from;
+      std::string& to;
+      ~TextReturn() {
+        if (from.capacity() > to.capacity()) {
+          to.swap(from);
+          to.clear();
+        }
+      }
+    } text_return{sc.text, text_buf_};
     bool ok = sc.parse_value(0, "", true) && sc.ok;
     if (ok) {
       sc.ws();
@@ -1140,7 +1228,11 @@ class ConnHandler {
       } else {
         fnv(body.data(), body.size());
       }
-      auto cl = srv_->gpu_direct_->count_lookup_text(sc.text);
+      // sc.text is moved into the admission queue here and in the two
+      // branches below; nothing after those points reads it (try_backend
+      // uses sc.model and the spans only) — keep it that way
+      auto cl = srv_->gpu_direct_->count_lookup_text(std::move(sc.text),
+                                                     &text_buf_);
       gpu_tokens = cl.tokens;
       srv_->stats_.gpu_tokens += (uint64_t)gpu_tokens;
       cache_slot = cl.slot;
@@ -1178,9 +1270,12 @@ class ConnHandler {
         // @ p99 2.1 ms, because the ~1 ms admission sleep paces the
         // 128 relay threads under the CPU quota (without it they all
         // stay runnable and earn CFS throttling).
-        pending_count_ = srv_->gpu_direct_->enqueue(sc.text);
+        pending_count_ = srv_->gpu_direct_->enqueue(std::move(sc.text));
       } else {
-        gpu_tokens = srv_->gpu_count(sc.text);
+        gpu_tokens = srv_->gpu_direct_ != nullptr
+                         ? srv_->gpu_direct_->count_text(std::move(sc.text),
+                                                         &text_buf_)
+                         : srv_->gpu_count(sc.text);
         srv_->stats_.gpu_tokens += (uint64_t)gpu_tokens;
       }
     }
@@ -1657,7 +1752,7 @@ class ConnHandler {
   // was in flight, so this wait is ~zero
   int64_t resolve_pending_count() {
     if (pending_count_ == nullptr) return 0;
-    auto cl = srv_->gpu_direct_->collect(pending_count_);
+    auto cl = srv_->gpu_direct_->collect(pending_count_, &text_buf_);
     pending_count_.reset();
     srv_->gpu_direct_->cache_release_slot(cl.slot);
     srv_->stats_.gpu_tokens += (uint64_t)cl.tokens;
@@ -1723,6 +1818,9 @@ class ConnHandler {
   // deferred admission count for the CURRENT request (enqueued before
   // upstream dispatch, collected in finish_usage)
   std::shared_ptr<DirectGpuBatcher::Waiter2> pending_count_;
+  // recycled buffer for the request's extracted chat text (see
+  // DirectGpuBatcher::Waiter2 for who may touch it when)
+  std::string text_buf_;
 
   friend class FastServer;
 };
@@ -1985,6 +2083,10 @@ std::vector<uint64_t> FastServer::gpu_direct_stats() const {
           gpu_direct_->stats_submit_us.load(),
           gpu_direct_->stats_wait_us.load(),
           gpu_direct_->stats_fulfill_us.load()};
+}
+
+uint64_t FastServer::gpu_direct_take_us() const {
+  return gpu_direct_ == nullptr ? 0 : gpu_direct_->stats_take_us.load();
 }
 
 bool FastServer::gpu_enabled() const {

@@ -140,6 +140,8 @@ class FastServer {
   // the batcher thread's per-phase wall-time sums (pipeline diagnosis);
   // zeros when direct admission is off
   std::vector<uint64_t> gpu_direct_stats() const;
+  // batcher take phase (wake with work available -> end of dequeue), summed
+  uint64_t gpu_direct_take_us() const;
   // cross-shard rate-limit sync hooks (aigw.parallel.StateSync bridge)
   std::vector<int64_t> rl_collect_deltas();
   void rl_apply_remote(const std::vector<int64_t>& others_spend);
