@@ -1,8 +1,9 @@
 """Comparators and input builders for the HIP kernel edge tests.
 
-Plain helper module (no tests here): tests/test_kernel_checks_cpu.py proves
-on the CPU that each comparator rejects deliberately wrong emulations, and
-tests/test_gpu_kernel_edges.py feeds them the real kernels' outputs.
+Plain helper module (no tests here): tests/test_kernel_checks_cpu.py and
+tests/test_kernel_checks_scoped_cpu.py prove on the CPU that each comparator
+rejects deliberately wrong emulations, and tests/test_gpu_kernel_edges.py
+and tests/test_gpu_cache_scoped_edges.py feed them the real kernels' outputs.
 
 Every bound below is an a-priori floating-point error bound for the
 operation, never a figure taken from the kernel under test.
@@ -49,57 +50,14 @@ def check_topk(hi, idx, index, q, allowed_rows=None) -> dict:
     exceed 100x that bound, otherwise an exact-row assertion would be a
     coin toss. Returns the worst figures seen, for reporting.
     """
-    from aigw.ops.semcache import _unorder
-
-    hi = _as_list(hi)
-    idx = _as_list(idx)
-    index64 = index.detach().cpu().to(torch.float64)
-    q64 = q.detach().cpu().to(torch.float64)
-    n_rows, dim = index64.shape
-    n_q = q64.shape[0]
-    assert len(hi) == n_q and len(idx) == n_q, (len(hi), len(idx), n_q)
-    S = index64 @ q64.T  # (N, B), exact up to fp64 rounding
-    row_norm = index64.norm(dim=1)
-    q_norm = q64.norm(dim=1)
-    max_row_norm = float(row_norm.max())
-    worst_err, worst_ratio, min_gap = 0.0, 0.0, float("inf")
-    for b in range(n_q):
-        col = S[:, b]
-        smax = float(col.max())
-        if allowed_rows is not None and allowed_rows[b] is not None:
-            allowed = sorted(int(r) for r in allowed_rows[b])
-            for r in allowed:
-                assert float(col[r]) == smax, (
-                    f"query {b}: allowed row {r} scores {float(col[r])!r}, "
-                    f"not the exact maximum {smax!r}")
-        else:
-            allowed = [int(col.argmax())]
-        # fitness of the inputs: best row outside the allowed set
-        if len(allowed) < n_rows:
-            rest = col.clone()
-            rest[allowed] = -float("inf")
-            gap = smax - float(rest.max())
-            gap_tol = dim * EPS23 * max_row_norm * float(q_norm[b])
-            assert gap > 100.0 * gap_tol, (
-                f"query {b}: inputs unfit for an exact-row check, top-1/top-2 "
-                f"gap {gap:.3e} <= 100 x {gap_tol:.3e}")
-            min_gap = min(min_gap, gap)
-        row = int(idx[b])
-        assert 0 <= row < n_rows, f"query {b}: row {row} out of range"
-        assert row in allowed, (
-            f"query {b}: got row {row} (exact score {float(col[row]):.6f}), "
-            f"want one of {allowed[:8]} (exact score {smax:.6f})")
-        score = _unorder(int(hi[b]))
-        tol = dim * EPS23 * float(row_norm[row]) * float(q_norm[b])
-        err = abs(score - smax)
-        assert err <= tol, (
-            f"query {b}: score {score!r} vs exact {smax!r}: "
-            f"|err| {err:.3e} > bound {tol:.3e}")
-        worst_err = max(worst_err, err)
-        if tol > 0:
-            worst_ratio = max(worst_ratio, err / tol)
-    return {"max_err": worst_err, "max_err_over_bound": worst_ratio,
-            "min_gap": min_gap}
+    # the unfiltered lookup is the scoped one with every cell eligible
+    n_rows, n_q = index.shape[0], q.shape[0]
+    stats = check_topk_scoped(
+        hi, idx, index, q, torch.zeros(n_rows, dtype=torch.int64),
+        torch.full((n_rows,), NEVER, dtype=torch.int32),
+        torch.zeros(n_q, dtype=torch.int64), 0, allowed_rows)
+    del stats["min_shadow_lead"]
+    return stats
 
 
 def unit_rows(n_rows: int, dim: int, dtype, seed: int) -> torch.Tensor:
@@ -132,6 +90,389 @@ def emulate_topk(index, q, row_mask=None, alias_second_pass=False):
         idx[128:] = idx[: max(idx.numel() - 128, 0)]
     hi = [order_float(v) for v in val.tolist()]
     return hi, idx.to(torch.int32)
+
+
+# ---------------------------------------------------------------------------
+# cache_topk_scoped
+# ---------------------------------------------------------------------------
+
+NEVER = 0x7FFFFFFF  # row_expiry of a row without a TTL
+INT32_MIN = -2 ** 31
+_INT64_MIN, _INT64_MAX = -2 ** 63, 2 ** 63 - 1
+
+
+def _i64_cpu(x) -> torch.Tensor:
+    if isinstance(x, torch.Tensor):
+        return x.detach().cpu().to(torch.int64)
+    return torch.tensor(list(x), dtype=torch.int64)
+
+
+def scoped_eligibility(row_scope, row_expiry, q_scope, now) -> torch.Tensor:
+    """(n_rows, n_q) bool on the CPU: row r may answer query j iff
+    row_expiry[r] > now and (q_scope[j] == 0 or row_scope[r] == q_scope[j])."""
+    rs, re, qs = _i64_cpu(row_scope), _i64_cpu(row_expiry), _i64_cpu(q_scope)
+    live = (re > int(now))[:, None]
+    match = (qs == 0)[None, :] | (rs[:, None] == qs[None, :])
+    return live & match
+
+
+def check_topk_scoped(hi, idx, index, q, row_scope, row_expiry, q_scope, now,
+                      allowed_rows=None, shadowed=()) -> dict:
+    """check_topk under the scope/TTL mask.
+
+    The reference is the fp64 product of the quantised operands with every
+    ineligible cell (scoped_eligibility) at -inf. A query nothing may
+    answer must come back as exactly idx -1 / hi 0. Any other query must
+    get the exact masked argmax (or a member of allowed_rows[b]), that row
+    must be eligible, and the score must lie within check_topk's bound,
+    dim * 2^-23 * |row| * |q|, of the exact masked maximum.
+
+    Input fitness: the masked top-1/top-2 gap must exceed 100x the bound,
+    and for every query listed in `shadowed` the unmasked maximum must
+    exceed the masked one by more than 100x the bound, i.e. an ineligible
+    row really does out-score the winner. Each assertion names the failed
+    property: "sentinel", "ineligible row", "wrong row" or "bound"."""
+    from aigw.ops.semcache import _unorder
+
+    hi = _as_list(hi)
+    idx = _as_list(idx)
+    index64 = index.detach().cpu().to(torch.float64)
+    q64 = q.detach().cpu().to(torch.float64)
+    n_rows, dim = index64.shape
+    n_q = q64.shape[0]
+    assert len(hi) == n_q and len(idx) == n_q, (len(hi), len(idx), n_q)
+    elig = scoped_eligibility(row_scope, row_expiry, q_scope, now)
+    assert tuple(elig.shape) == (n_rows, n_q), tuple(elig.shape)
+    S = index64 @ q64.T
+    row_norm = index64.norm(dim=1)
+    q_norm = q64.norm(dim=1)
+    max_row_norm = float(row_norm.max()) if n_rows else 0.0
+    shadowed = {int(b) for b in shadowed}
+    worst_err, worst_ratio = 0.0, 0.0
+    min_gap, min_lead = float("inf"), float("inf")
+    for b in range(n_q):
+        col, ok = S[:, b], elig[:, b]
+        row = int(idx[b])
+        if not bool(ok.any()):
+            assert b not in shadowed, (
+                f"query {b}: inputs unfit, flagged shadowed but no row is eligible")
+            assert row == -1 and int(hi[b]) == 0, (
+                f"query {b}: sentinel: no row is eligible, want idx -1 / hi 0, "
+                f"got idx {row} / hi {int(hi[b])}")
+            continue
+        masked = col.masked_fill(~ok, -float("inf"))
+        smax = float(masked.max())
+        if allowed_rows is not None and allowed_rows[b] is not None:
+            allowed = sorted(int(r) for r in allowed_rows[b])
+            for r in allowed:
+                assert float(masked[r]) == smax, (
+                    f"query {b}: allowed row {r} scores {float(masked[r])!r} under "
+                    f"the mask, not the exact maximum {smax!r}")
+        else:
+            allowed = [int(masked.argmax())]
+        gap_tol = dim * EPS23 * max_row_norm * float(q_norm[b])
+        rest = masked.clone()
+        rest[allowed] = -float("inf")
+        second = float(rest.max())
+        if second > -float("inf"):
+            gap = smax - second
+            assert gap > 100.0 * gap_tol, (
+                f"query {b}: inputs unfit for an exact-row check, masked "
+                f"top-1/top-2 gap {gap:.3e} <= 100 x {gap_tol:.3e}")
+            min_gap = min(min_gap, gap)
+        if b in shadowed:
+            lead = float(col.max()) - smax
+            assert lead > 100.0 * gap_tol, (
+                f"query {b}: inputs unfit, flagged shadowed but the best ineligible "
+                f"row leads the masked maximum by {lead:.3e} <= 100 x {gap_tol:.3e}")
+            min_lead = min(min_lead, lead)
+        assert row != -1, (
+            f"query {b}: sentinel: got idx -1 / hi {int(hi[b])} although row "
+            f"{allowed[0]} is eligible (exact score {smax:.6f})")
+        assert 0 <= row < n_rows, f"query {b}: row {row} out of range"
+        assert bool(ok[row]), (
+            f"query {b}: ineligible row {row} (scope {int(_i64_cpu(row_scope)[row])}, "
+            f"expiry {int(_i64_cpu(row_expiry)[row])}) returned for scope "
+            f"{int(_i64_cpu(q_scope)[b])} at now {int(now)}; want one of {allowed[:8]}")
+        assert row in allowed, (
+            f"query {b}: wrong row: got row {row} (exact score {float(col[row]):.6f}), "
+            f"want one of {allowed[:8]} (exact score {smax:.6f})")
+        score = _unorder(int(hi[b]))
+        tol = dim * EPS23 * float(row_norm[row]) * float(q_norm[b])
+        err = abs(score - smax)
+        assert err <= tol, (
+            f"query {b}: score {score!r} vs exact {smax!r}: "
+            f"|err| {err:.3e} > bound {tol:.3e}")
+        worst_err = max(worst_err, err)
+        if tol > 0:
+            worst_ratio = max(worst_ratio, err / tol)
+    return {"max_err": worst_err, "max_err_over_bound": worst_ratio,
+            "min_gap": min_gap, "min_shadow_lead": min_lead}
+
+
+SCOPED_MUTANTS = (
+    "filter_after_argmax",        # a
+    "mask_after_group_max",       # b
+    "expiry_ge",                  # c
+    "wildcard_ignores_expiry",    # d
+    "second_pass_first_scopes",   # e
+    "scope_low32",                # f
+    "partial_group_ineligible",   # g
+    "partial_group_first_tags",   # h
+    "swapped_tile_tags",          # i
+    "no_row_returns_row0",        # j
+    "nonpositive_lost",           # k
+)
+
+
+def emulate_topk_scoped(index, q, row_scope, row_expiry, q_scope, now, mutant=None):
+    """Pure-torch fp32 emulation of cache_topk_scoped's contract -> (hi, idx).
+
+    `mutant` (one of SCOPED_MUTANTS) exists only so the CPU self-tests can
+    build deliberately wrong variants of the kernel's structure: 4-row lane
+    groups, 16-row tiles with ping-pong tag buffers, 128-query passes."""
+    assert mutant is None or mutant in SCOPED_MUTANTS, mutant
+    s = index.to(torch.float32) @ q.to(torch.float32).T  # (N, B)
+    n_rows, n_q = s.shape
+    rs, re, qs = _i64_cpu(row_scope), _i64_cpu(row_expiry), _i64_cpu(q_scope)
+    in_range = torch.ones(n_rows, dtype=torch.bool)
+    rows = torch.arange(n_rows)
+    tail0 = (n_rows // 4) * 4  # first row of the partial 4-row group, if any
+    if mutant == "partial_group_ineligible":
+        in_range = rows < tail0
+    if mutant == "partial_group_first_tags" and tail0 < n_rows:
+        rs, re = rs.clone(), re.clone()
+        rs[tail0:] = rs[tail0]
+        re[tail0:] = re[tail0]
+    if mutant == "swapped_tile_tags":
+        src = rows ^ 16
+        in_range = src < n_rows
+        src = src.clamp_max(n_rows - 1)
+        rs, re = rs[src], re[src]
+    if mutant == "second_pass_first_scopes":
+        qs = qs.clone()
+        qs[128:] = qs[: max(n_q - 128, 0)]
+    live = (re >= now) if mutant == "expiry_ge" else (re > now)
+    wild = (qs == 0)[None, :]
+    if mutant == "scope_low32":
+        match = wild | ((rs & 0xFFFFFFFF)[:, None] == (qs & 0xFFFFFFFF)[None, :])
+    else:
+        match = wild | (rs[:, None] == qs[None, :])
+    elig = live[:, None] & match
+    if mutant == "wildcard_ignores_expiry":
+        elig = elig | wild.expand(n_rows, n_q)
+    elig = elig & in_range[:, None]
+    if mutant == "nonpositive_lost":
+        elig = elig & (s > 0)
+    neg = torch.full_like(s, -float("inf"))
+    cols = torch.arange(n_q)
+    if mutant == "filter_after_argmax":
+        val, idx = s.max(dim=0)
+        found = elig[idx, cols]
+    elif mutant == "mask_after_group_max":
+        pad = (-n_rows) % 4
+        sp = torch.cat([s, neg[:pad]])
+        ep = torch.cat([elig, torch.zeros(pad, n_q, dtype=torch.bool)])
+        gval, gr = sp.view(-1, 4, n_q).max(dim=1)  # unfiltered best of each group
+        grow = gr + 4 * torch.arange(sp.shape[0] // 4)[:, None]
+        gok = ep[grow, cols[None, :]]
+        val, g = torch.where(gok, gval, neg[: gval.shape[0]]).max(dim=0)
+        idx = grow[g, cols]
+        found = gok.any(dim=0)
+    else:
+        val, idx = torch.where(elig, s, neg).max(dim=0)
+        found = elig.any(dim=0)
+    hi, out = [], []
+    for b in range(n_q):
+        if bool(found[b]):
+            hi.append(order_float(float(val[b])))
+            out.append(int(idx[b]))
+        elif mutant == "no_row_returns_row0":
+            hi.append(order_float(float(s[0, b])))
+            out.append(0)
+        else:
+            hi.append(0)
+            out.append(-1)
+    return hi, torch.tensor(out, dtype=torch.int32)
+
+
+def scope_ids(n: int, seed: int, bits: int = 64) -> list[int]:
+    """n distinct seeded scope ids over the full signed int64 range (as the
+    first 8 bytes of a SHA-256 are), about half of them negative; never 0
+    (the wildcard), and never a value whose foreign_scope() would overflow
+    or hit 0. bits=31 gives small positive ids instead (only for the
+    self-tests that show what 64-bit ids add)."""
+    rng = np.random.default_rng(seed)
+    out, seen = [], {0, -1, 1, _INT64_MIN, _INT64_MAX}
+    while len(out) < n:
+        if bits == 64:
+            v = int(rng.integers(_INT64_MIN, _INT64_MAX, dtype=np.int64, endpoint=True))
+        else:
+            v = int(rng.integers(2, 2 ** bits - 2))
+        if v not in seen:
+            seen.add(v)
+            out.append(v)
+    return out
+
+
+def foreign_scope(s: int, k: int) -> int:
+    """A scope id that is not `s` but is close to it in one of four ways:
+    the low 32 bits equal, all but the sign bit equal, the negation, the
+    successor."""
+    k %= 4
+    if k == 0:
+        v = s ^ (1 << 32)
+    elif k == 1:
+        v = s + 2 ** 63 if s < 0 else s - 2 ** 63  # s ^ (1 << 63) as signed
+    elif k == 2:
+        v = -s
+    else:
+        v = s + 1
+    assert v != s and v != 0 and _INT64_MIN <= v <= _INT64_MAX, (s, k, v)
+    return v
+
+
+class ScopedQuery:
+    """One query of a planted masked case.
+
+    winner      row that must come back, or None for a query nothing may
+                answer (its scope then matches no row)
+    scope       the query's scope id, 0 = wildcard
+    decoy       row that gets an exact copy of the query, or None
+    decoy_scope, decoy_expiry   the decoy's tag (decoy_scope None = `scope`)
+    winner_expiry               the winner's expiry (None = builder's choice)
+    negative    the winner is -0.5 * query and `runner` is -query, the only
+                two rows of the query's scope: the masked maximum is < 0
+    """
+
+    def __init__(self, winner, scope, decoy=None, decoy_scope=None,
+                 decoy_expiry=NEVER, winner_expiry=None, negative=False, runner=None):
+        self.winner, self.scope, self.decoy = winner, int(scope), decoy
+        self.decoy_scope = self.scope if decoy_scope is None else int(decoy_scope)
+        self.decoy_expiry, self.winner_expiry = int(decoy_expiry), winner_expiry
+        self.negative, self.runner = negative, runner
+        assert (runner is not None) == negative
+
+
+DECOY_KINDS = ("foreign", "now", "past", "wild")
+
+
+def scoped_query(winner, scope, decoy, kind, now, k=0) -> ScopedQuery:
+    """A ScopedQuery whose decoy is ineligible in the way `kind` says:
+    foreign scope (variant k of foreign_scope), expiry == now, expiry < now,
+    or a wildcard query with an expired decoy."""
+    if decoy is None:
+        return ScopedQuery(winner, scope)
+    if kind == "foreign":
+        return ScopedQuery(winner, scope, decoy, foreign_scope(scope, k))
+    if kind == "now":
+        return ScopedQuery(winner, scope, decoy, decoy_expiry=now)
+    if kind == "past":
+        return ScopedQuery(winner, scope, decoy,
+                           decoy_expiry=(now - 1, 0, INT32_MIN)[k % 3] if now > 0 else now - 1)
+    assert kind == "wild", kind
+    return ScopedQuery(winner, 0, decoy, decoy_scope=scope, decoy_expiry=now - 1 - k % 2)
+
+
+class ScopedCase:
+    """Tensors of a planted masked case (CPU) plus what the tests need to
+    know about it: winners[b] (-1 = nothing may answer) and the queries
+    whose decoy out-scores the winner while ineligible."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def tensors(self):
+        return (self.index, self.q, self.row_scope, self.row_expiry, self.q_scope,
+                self.now)
+
+
+def scoped_case(n_rows: int, dim: int, dtype, queries, seed: int,
+                now: int = 1000) -> ScopedCase:
+    """Planted masked inputs. Background: seeded unit rows tagged with the
+    scopes of the call's own scoped queries, one row in eight dead. The
+    query for winner w is normalize(index[w] + 0.5 * unit noise), quantised:
+    ~0.9 on its winner, <= ~0.43 on any other background row. A decoy is a
+    copy of the quantised query (score |q|^2) under a tag that makes it
+    ineligible. Every row has at most one role per call."""
+    g = torch.Generator().manual_seed(seed + 7919)  # not unit_rows' stream
+    index = unit_rows(n_rows, dim, dtype, seed).to(torch.float32)
+    n_q = len(queries)
+    roles = {}
+
+    def claim(r, what):
+        assert r is not None and 0 <= r < n_rows, (what, r, n_rows)
+        assert r not in roles, f"row {r}: {what} collides with {roles[r]}"
+        roles[r] = what
+
+    for b, sp in enumerate(queries):
+        if sp.winner is not None:
+            claim(sp.winner, f"winner of query {b}")
+        if sp.decoy is not None:
+            claim(sp.decoy, f"decoy of query {b}")
+        if sp.runner is not None:
+            claim(sp.runner, f"runner-up of query {b}")
+    # background tags: scopes shared with the queries, so each scoped query
+    # has eligible background rows besides its winner
+    shared = [sp.scope for sp in queries
+              if sp.scope != 0 and sp.winner is not None and not sp.negative]
+    if not shared:
+        shared = scope_ids(3, seed + 1)
+    pick = torch.randint(0, len(shared), (n_rows,), generator=g).tolist()
+    row_scope = [shared[i] for i in pick]
+    row_expiry = [min(now + 1 + int(v), NEVER) for v in
+                  torch.randint(0, 50, (n_rows,), generator=g).tolist()]
+    dead = (now, now - 1, min(now, 0), INT32_MIN)
+    for r in range(n_rows):
+        if r % 7 == 3:
+            row_expiry[r] = NEVER
+        if r % 8 == 5:
+            row_expiry[r] = dead[(r // 8) % 4]
+    noise = torch.nn.functional.normalize(torch.randn(n_q, dim, generator=g), dim=1)
+    q = torch.empty(n_q, dim)
+    for b, sp in enumerate(queries):
+        anchor = sp.winner if (sp.winner is not None and not sp.negative) else None
+        base = index[anchor] if anchor is not None else torch.zeros(dim)
+        v = torch.nn.functional.normalize(base + (0.5 if anchor is not None else 1.0)
+                                          * noise[b], dim=0)
+        q[b] = v.to(torch.bfloat16).to(dtype).to(torch.float32)
+    winners, shadowed = [], []
+    for b, sp in enumerate(queries):
+        winners.append(-1 if sp.winner is None else sp.winner)
+        if sp.winner is not None:
+            if sp.negative:
+                index[sp.winner] = -0.5 * q[b]
+                index[sp.runner] = -q[b]
+                row_scope[sp.runner], row_expiry[sp.runner] = sp.scope, NEVER
+            row_scope[sp.winner] = sp.scope if sp.scope != 0 else row_scope[sp.winner]
+            row_expiry[sp.winner] = (sp.winner_expiry if sp.winner_expiry is not None
+                                     else (min(now + 1, NEVER), NEVER)[b % 2])
+        if sp.decoy is not None:
+            index[sp.decoy] = q[b]
+            row_scope[sp.decoy], row_expiry[sp.decoy] = sp.decoy_scope, sp.decoy_expiry
+            eligible = sp.decoy_expiry > now and sp.scope in (0, sp.decoy_scope)
+            if sp.winner is not None and not eligible:
+                shadowed.append(b)
+    return ScopedCase(
+        index=index.to(torch.bfloat16).to(dtype),
+        q=q.to(torch.bfloat16).to(dtype),
+        row_scope=torch.tensor(row_scope, dtype=torch.int64),
+        row_expiry=torch.tensor(row_expiry, dtype=torch.int32),
+        q_scope=torch.tensor([sp.scope for sp in queries], dtype=torch.int64),
+        now=now, winners=winners, shadowed=shadowed)
+
+
+def pair_queries(winners, scopes, n_rows, now, kinds=DECOY_KINDS, start=0):
+    """One ScopedQuery per winner with its decoy at the pair partner w ^ 1
+    (same 4-row lane group, below an odd winner and above an even one) where
+    that row exists; decoy kinds and foreign-scope variants cycle."""
+    out = []
+    for i, (w, s) in enumerate(zip(winners, scopes)):
+        d = w ^ 1
+        k = start + i
+        out.append(scoped_query(w, s, d if d < n_rows else None,
+                                kinds[k % len(kinds)], now, k // len(kinds)))
+    return out
 
 
 # ---------------------------------------------------------------------------
