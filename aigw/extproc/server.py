@@ -22,6 +22,7 @@ dropped on streamed responses.
 from __future__ import annotations
 
 import asyncio
+import dataclasses
 import json
 import logging
 import time
@@ -726,7 +727,7 @@ class GatewayServer:
                 request, endpoint, route, headers, body, stream, start,
                 model=model, gpu_input_tokens=gpu_input_tokens, cache_key_vec=cache_key_vec,
                 cache_tag=cache_tag,
-                span=span, raw=raw,
+                span=span, raw=raw, chat_text=chat_text,
             )
             if span is not None:
                 self.tracer.end_span(span, error=None if resp.status < 500 else f"status {resp.status}")
@@ -752,6 +753,7 @@ class GatewayServer:
         cache_tag: bytes = b"",
         span=None,
         raw: bytes = b"",
+        chat_text: bytes = b"",
     ) -> web.StreamResponse:
         rt = self.runtime
         assert self._session is not None, "GatewayServer.start() not called"
@@ -785,9 +787,33 @@ class GatewayServer:
                     st = self._ep_stats.setdefault(b.name, [0, 0.0])
                     row = [st[1], 100000.0, float(st[0]), float(st[0])]
                 stats_rows.append(row)
-            pick = await self.gpu.pick_endpoint(
-                stats_rows, float(gpu_input_tokens or 256)
-            )
+            pick = None
+            pc = route.route.prefix_cache
+            if pc is not None and chat_text and hasattr(self.gpu, "pick_endpoint_prefix"):
+                # prefix-cache-aware pick: the replica that already holds
+                # the prompt's leading token blocks scores higher. Backend
+                # names key the index; member_name() keeps them stable
+                # across pool re-resolution.
+                try:
+                    pick = await self.gpu.pick_endpoint_prefix(
+                        route.route.name, [b.name for b in tier0], stats_rows,
+                        chat_text, float(gpu_input_tokens or 256),
+                        settings=dataclasses.asdict(pc),
+                    )
+                    if not 0 <= pick < len(tier0):
+                        raise ValueError(f"prefix pick {pick} out of range")
+                    name = (route.route.name,)
+                    self.metrics._child(self.metrics.prefix_matched_tokens, name).inc(
+                        getattr(pick, "matched_tokens", 0))
+                    self.metrics._child(self.metrics.prefix_picked_tokens, name).inc(
+                        getattr(pick, "prompt_tokens", 0) or gpu_input_tokens)
+                except Exception:
+                    logger.exception("prefix-cache pick failed; using the plain picker")
+                    pick = None
+            if pick is None:
+                pick = await self.gpu.pick_endpoint(
+                    stats_rows, float(gpu_input_tokens or 256)
+                )
             ordered = [tier0[pick]] + [b for i, b in enumerate(tier0) if i != pick]
 
             def _gen():

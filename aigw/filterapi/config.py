@@ -314,6 +314,19 @@ class InferencePool:
 
 
 @dataclass
+class PrefixCache:
+    """Prefix-cache-aware endpoint picking (the EPP's prefix-cache-scorer):
+    the picker prefers the replica that was already sent a prompt with the
+    same leading token blocks. Only with endpointPicker: true."""
+
+    block_tokens: int = 16  # tokens per hashed block: 8, 16, 32 or 64
+    max_blocks: int = 256  # blocks hashed per prompt (<= 256)
+    buckets: int = 65536  # index buckets of 16 slots; a power of two
+    ttl_s: float = 300.0  # seconds an index entry stays live (a guess)
+    weight: float = 1.0  # score weight of the matched fraction (a guess)
+
+
+@dataclass
 class Route:
     """One routing rule (filterconfig.go Config.Rules).
 
@@ -334,6 +347,8 @@ class Route:
     # (replaces the reference's external EPP service —
     # extensionserver/inferencepool.go:39-54).
     endpoint_picker: bool = False
+    # Adds the on-GPU prefix block index to the picker's score
+    prefix_cache: Optional[PrefixCache] = None
     # Dynamic member resolution; resolved members are APPENDED to the
     # static `backends` list by aigw.extproc.pool.PoolManager
     pool: Optional[InferencePool] = None
@@ -546,6 +561,28 @@ def _parse_backend(d, ctx) -> Backend:
     return Backend(**kw)
 
 
+def _parse_prefix_cache(d, ctx) -> PrefixCache:
+    def _int(v):
+        return isinstance(v, int) and not isinstance(v, bool)
+
+    def _num(v):
+        return isinstance(v, (int, float)) and not isinstance(v, bool)
+
+    pc = PrefixCache(**_dc(PrefixCache, d, ctx))
+    if not _int(pc.block_tokens) or pc.block_tokens not in (8, 16, 32, 64):
+        raise ConfigError(f"{ctx}: blockTokens must be 8, 16, 32 or 64")
+    if not _int(pc.max_blocks) or not 1 <= pc.max_blocks <= 256:
+        raise ConfigError(f"{ctx}: maxBlocks must be in [1, 256]")
+    if (not _int(pc.buckets) or pc.buckets < 1 or pc.buckets & (pc.buckets - 1)
+            or pc.buckets > 1 << 27):
+        raise ConfigError(f"{ctx}: buckets must be a power of two, at most 2^27")
+    if not _num(pc.ttl_s) or not pc.ttl_s > 0:
+        raise ConfigError(f"{ctx}: ttlS must be positive")
+    if not _num(pc.weight) or not pc.weight >= 0:
+        raise ConfigError(f"{ctx}: weight must not be negative")
+    return pc
+
+
 def _parse_route(d, ctx) -> Route:
     kw = _dc(Route, d, ctx)
     if "name" not in kw:
@@ -564,6 +601,10 @@ def _parse_route(d, ctx) -> Route:
         kw["header_mutation"] = HeaderMutation(
             **_dc(HeaderMutation, kw["header_mutation"], f"{ctx}.headerMutation")
         )
+    if kw.get("prefix_cache") is not None:
+        kw["prefix_cache"] = _parse_prefix_cache(kw["prefix_cache"], f"{ctx}.prefixCache")
+        if not kw.get("endpoint_picker"):
+            raise ConfigError(f"{ctx}.prefixCache: requires endpointPicker: true")
     if kw.get("pool") is not None:
         pkw = _dc(InferencePool, kw["pool"], f"{ctx}.pool")
         if "schema" in pkw:

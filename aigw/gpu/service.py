@@ -17,6 +17,9 @@ Wire protocol: 4-byte little-endian length + msgpack map. Ops:
   {id, op:"invalidate"}                           -> {id, rows:int}
   {id, op:"tokenize", text:bytes}                 -> {id, ids:[int]}
   {id, op:"pick", stats:[[f,f,f,f]], predicted:f} -> {id, index:int}
+  {id, op:"pick_prefix", pool:str, members:[str], stats:[[f,f,f,f]],
+   text:bytes, predicted:f, settings:{..}|nil}    -> {id, index:int,
+                                                      matched:int, tokens:int}
 Replies may arrive out of order (matched by id).
 Optional fields (index-scoped cache): lookup_batch takes scopes:[bytes|nil]
 aligned with texts; insert takes scope:bytes and ttl_s:float; invalidate
@@ -134,6 +137,14 @@ class GPUServiceHost:
                 out["index"] = await self.gpu.pick_endpoint(
                     msg["stats"], float(msg["predicted"])
                 )
+            elif op == "pick_prefix":
+                pick = await self.gpu.pick_endpoint_prefix(
+                    msg["pool"], msg["members"], msg["stats"], msg["text"],
+                    float(msg["predicted"]), settings=msg.get("settings"),
+                )
+                out["index"] = int(pick)
+                out["matched"] = getattr(pick, "matched_tokens", 0)
+                out["tokens"] = getattr(pick, "prompt_tokens", 0)
             else:
                 out["error"] = f"unknown op {op!r}"
         except Exception as e:  # pragma: no cover - defensive
@@ -302,6 +313,18 @@ class RemoteGPUClient:
              "predicted": float(predicted)}
         )
         return reply["index"]
+
+    async def pick_endpoint_prefix(self, pool: str, members, stats_rows, text: bytes,
+                                   predicted: float, settings=None) -> int:
+        from aigw.gpu.services import PrefixPick
+
+        reply = await self._call(
+            {"op": "pick_prefix", "pool": pool, "members": list(members),
+             "stats": [list(map(float, r)) for r in stats_rows],
+             "text": bytes(text or b" "), "predicted": float(predicted),
+             "settings": settings}
+        )
+        return PrefixPick(reply["index"], reply.get("matched", 0), reply.get("tokens", 0))
 
     def close(self):
         if self._pump_task:

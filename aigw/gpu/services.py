@@ -51,6 +51,17 @@ def _scope_id(scope) -> int:
     return scope_id(bytes(scope))
 
 
+class PrefixPick(int):
+    """Replica row picked by the prefix-cache-aware scorer: an int that
+    also says how many of the prompt's tokens the replica had seen."""
+
+    def __new__(cls, index: int, matched_tokens: int = 0, prompt_tokens: int = 0):
+        self = super().__new__(cls, index)
+        self.matched_tokens = int(matched_tokens)
+        self.prompt_tokens = int(prompt_tokens)
+        return self
+
+
 @dataclass
 class _Pending:
     """One queued work item: a BATCH of texts sharing a future (single
@@ -109,6 +120,7 @@ class GPUServices:
         # event polling adds per-batch latency. Kept behind an opt-in for
         # core-constrained deployments.
         self.async_counts = _os.environ.get("AIGW_GPU_ASYNC_PATH", "") == "1"
+        self._prefix: dict = {}  # pool name -> PrefixIndex, built lazily
         self._pending: list[_Pending] = []
         self._pending_texts = 0
         self._flush_handle = None
@@ -317,6 +329,76 @@ class GPUServices:
             return int(hip.kv_score_assign(stats, pred, 1.0, 0.1, 0.05).cpu()[0])
 
         return await loop.run_in_executor(self._executor, run)
+
+    # ---- prefix-cache-aware picking ------------------------------------------
+
+    def _prefix_index(self, pool: str, settings: Optional[dict]):
+        """The pool's PrefixIndex, built on first use from the route's
+        prefixCache settings (GPU executor thread only)."""
+        idx = self._prefix.get(pool)
+        if idx is None:
+            from aigw.ops.prefixindex import PrefixIndex
+
+            s = settings or {}
+            idx = PrefixIndex(
+                pool,
+                block_tokens=int(s.get("block_tokens", 16)),
+                max_blocks=int(s.get("max_blocks", 256)),
+                buckets=int(s.get("buckets", 65536)),
+                ttl_s=s.get("ttl_s", 300.0),
+                weight=float(s.get("weight", 1.0)),
+                device=self.device,
+                _hip=self.tokenizer.hip,
+            )
+            self._prefix[pool] = idx
+        return idx
+
+    def _assign_prefix(self, pool, members, stats, texts, predicted, settings):
+        """GPU executor thread: tokenise (one packed, sync-free launch
+        chain), hash, match, score, insert; ONE host sync at the end."""
+        idx = self._prefix_index(pool, settings)
+        texts = [t or b" " for t in texts]
+        counts, out_ids, req_off, _ev = self.tokenizer.encode_batch_async(texts)
+        if not torch.is_tensor(stats):
+            stats = torch.tensor(stats, dtype=torch.float32)
+        stats = stats.to(self.device, torch.float32).contiguous()
+        if predicted is None:
+            pred = counts.to(torch.float32)  # the prompts' own token counts
+        else:
+            if not torch.is_tensor(predicted):
+                predicted = torch.tensor(list(predicted), dtype=torch.float32)
+            pred = predicted.to(self.device, torch.float32).contiguous()
+        assign, hit, _nb = idx.assign(
+            members, stats, pred, out_ids, req_off, sum(len(t) for t in texts)
+        )
+        matched = torch.minimum(hit * idx.block_tokens, counts)
+        host = torch.stack([assign, matched, counts]).cpu().tolist()  # the sync
+        return [PrefixPick(a, m, c) for a, m, c in zip(*host)]
+
+    async def assign_replicas_prefix(self, pool: str, members, stats, texts,
+                                     predicted=None, settings: Optional[dict] = None):
+        """Batched prefix-cache-aware assignment for one pool: texts[i]
+        goes to replica row result[i] of ``stats`` (rows in ``members``
+        order). ``predicted`` (tokens per request) defaults to the
+        prompts' own token counts. Each result is a PrefixPick."""
+        loop = asyncio.get_running_loop()
+        return await loop.run_in_executor(
+            self._executor, self._assign_prefix, pool, list(members), stats,
+            list(texts), predicted, settings,
+        )
+
+    async def pick_endpoint_prefix(self, pool: str, members, stats_rows, text: bytes,
+                                   predicted: float,
+                                   settings: Optional[dict] = None) -> int:
+        """pick_endpoint with the prefix-hit term: prefers the replica
+        whose KV cache already holds the longest prefix of ``text``."""
+        picks = await self.assign_replicas_prefix(
+            pool, members, stats_rows, [text], [float(predicted)], settings
+        )
+        return picks[0]
+
+    def prefix_stats(self) -> dict:
+        return {pool: idx.stats() for pool, idx in self._prefix.items()}
 
     async def assign_replicas(self, stats: torch.Tensor, predicted: torch.Tensor):
         loop = asyncio.get_running_loop()

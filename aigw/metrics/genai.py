@@ -85,6 +85,18 @@ class GenAIMetrics:
             ["route"],
             registry=self.registry,
         )
+        self.prefix_matched_tokens = Counter(
+            "aigw_prefix_cache_matched_tokens_total",
+            "Prompt tokens the picked replica had already seen (prefix index)",
+            ["route"],
+            registry=self.registry,
+        )
+        self.prefix_picked_tokens = Counter(
+            "aigw_prefix_cache_picked_tokens_total",
+            "Prompt tokens of requests placed by the prefix-cache-aware picker",
+            ["route"],
+            registry=self.registry,
+        )
         self.cache_events = Counter(
             "aigw_semantic_cache_events_total",
             "Semantic cache hits/misses",

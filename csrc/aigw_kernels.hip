@@ -13,6 +13,9 @@
 //   3. Fused MFMA similarity + argmax over the HBM-resident cache index.
 //   4. KV-occupancy endpoint scorer — replaces the external EPP service
 //      (extensionserver/inferencepool.go:39-54).
+//   5. Prefix-cache-aware picking: chained token-block hashes and an
+//      HBM-resident block -> replica-mask index feeding the scorer (the
+//      EPP's prefix-cache-scorer, on real token blocks).
 //
 // CDNA4 specifics used (per the MI355X HIP guide): 64-wide wavefronts
 // (64-bit ballot masks), __builtin_amdgcn_mfma_f32_16x16x32_bf16 with the
@@ -48,6 +51,12 @@ static inline hipStream_t current_stream() {
 // ---------------------------------------------------------------------------
 
 #include "cache_kernels.cuh"
+
+// ---------------------------------------------------------------------------
+// 5. Prefix-cache-aware endpoint picking (block hashes, HBM block index)
+// ---------------------------------------------------------------------------
+
+#include "prefix_kernels.cuh"
 
 // ---------------------------------------------------------------------------
 // Host wrappers
@@ -507,6 +516,184 @@ at::Tensor kv_score_assign(at::Tensor stats, at::Tensor pred_tokens, double w_kv
   return assign;
 }
 
+// ---- prefix index ----------------------------------------------------------
+
+#define PREFIX_INSERT_WAVES 512
+
+static void check_prefix_table(const at::Tensor& keys, const at::Tensor& masks,
+                               const at::Tensor& stamps, const char* who) {
+  check_cuda(keys, "keys");
+  check_cuda(masks, "masks");
+  check_cuda(stamps, "stamps");
+  TORCH_CHECK(keys.scalar_type() == at::kLong && keys.dim() == 1, who,
+              ": keys must be int64[n_buckets*16]");
+  TORCH_CHECK(masks.scalar_type() == at::kLong && masks.dim() == 1 &&
+                  masks.size(0) == keys.size(0),
+              who, ": masks must be int64[n_buckets*16]");
+  TORCH_CHECK(stamps.scalar_type() == at::kInt && stamps.dim() == 1 &&
+                  stamps.size(0) == keys.size(0),
+              who, ": stamps must be int32[n_buckets*16]");
+  long long n_slots = keys.size(0);
+  long long n_buckets = n_slots / PREFIX_SLOTS;
+  TORCH_CHECK(n_slots % PREFIX_SLOTS == 0 && n_buckets >= 1 &&
+                  (n_buckets & (n_buckets - 1)) == 0 && n_buckets <= (1LL << 27),
+              who, ": n_buckets must be a power of two, at most 2^27");
+  TORCH_CHECK(masks.device() == keys.device() && stamps.device() == keys.device(), who,
+              ": all tensors must be on one device");
+}
+
+static void check_prefix_hashes(const at::Tensor& hashes, const at::Tensor& n_blocks,
+                                const at::Tensor& table, const char* who) {
+  check_cuda(hashes, "hashes");
+  check_cuda(n_blocks, "n_blocks");
+  TORCH_CHECK(hashes.scalar_type() == at::kLong && hashes.dim() == 2, who,
+              ": hashes must be int64[n_req, max_blocks]");
+  TORCH_CHECK(hashes.size(1) >= 1 && hashes.size(1) <= PREFIX_MAX_BLOCKS, who,
+              ": max_blocks must be in [1, 256]");
+  TORCH_CHECK(n_blocks.scalar_type() == at::kInt && n_blocks.dim() == 1 &&
+                  n_blocks.size(0) == hashes.size(0),
+              who, ": n_blocks must be int32[n_req]");
+  TORCH_CHECK(hashes.size(0) <= (1 << 20), who, ": at most 2^20 requests per call");
+  TORCH_CHECK(hashes.device() == table.device() && n_blocks.device() == table.device(),
+              who, ": all tensors must be on one device");
+}
+
+std::vector<at::Tensor> prefix_block_hashes(at::Tensor out_ids, at::Tensor req_off,
+                                            int64_t n_bytes, int64_t block_tokens,
+                                            int64_t max_blocks, int64_t salt) {
+  check_cuda(out_ids, "out_ids");
+  check_cuda(req_off, "req_off");
+  TORCH_CHECK(out_ids.scalar_type() == at::kInt && out_ids.dim() == 1,
+              "prefix_block_hashes: out_ids must be int32[n_bytes]");
+  TORCH_CHECK(req_off.scalar_type() == at::kLong && req_off.dim() == 1,
+              "prefix_block_hashes: req_off must be int64[n_req]");
+  TORCH_CHECK(out_ids.device() == req_off.device(),
+              "prefix_block_hashes: all tensors must be on one device");
+  TORCH_CHECK(n_bytes >= 0 && n_bytes <= out_ids.numel(),
+              "prefix_block_hashes: n_bytes must be in [0, out_ids.numel()]");
+  TORCH_CHECK(block_tokens == 8 || block_tokens == 16 || block_tokens == 32 ||
+                  block_tokens == 64,
+              "prefix_block_hashes: block_tokens must be 8, 16, 32 or 64");
+  TORCH_CHECK(max_blocks >= 1 && max_blocks <= PREFIX_MAX_BLOCKS,
+              "prefix_block_hashes: max_blocks must be in [1, 256]");
+  long long n_req = req_off.numel();
+  TORCH_CHECK(n_req <= (1 << 20), "prefix_block_hashes: at most 2^20 requests per call");
+  auto hashes = at::empty({n_req, max_blocks},
+                          at::TensorOptions().dtype(at::kLong).device(out_ids.device()));
+  auto n_blocks = at::empty({n_req},
+                            at::TensorOptions().dtype(at::kInt).device(out_ids.device()));
+  if (n_req == 0) return {hashes, n_blocks};
+  hipLaunchKernelGGL(prefix_block_hash_kernel, dim3((unsigned)n_req), dim3(256), 0,
+                     current_stream(), out_ids.data_ptr<int32_t>(),
+                     req_off.data_ptr<int64_t>(), (int)n_req, (long long)n_bytes,
+                     (int)block_tokens, (int)max_blocks, (pfx_u64)salt,
+                     hashes.data_ptr<int64_t>(), n_blocks.data_ptr<int32_t>());
+  return {hashes, n_blocks};
+}
+
+at::Tensor prefix_match(at::Tensor keys, at::Tensor masks, at::Tensor stamps,
+                        at::Tensor hashes, at::Tensor n_blocks, int64_t live_mask,
+                        int64_t now, int64_t ttl) {
+  check_prefix_table(keys, masks, stamps, "prefix_match");
+  check_prefix_hashes(hashes, n_blocks, keys, "prefix_match");
+  TORCH_CHECK(now >= 0 && now <= INT32_MAX && ttl >= 0 && ttl <= INT32_MAX,
+              "prefix_match: now and ttl must fit a non-negative int32");
+  long long n_req = hashes.size(0);
+  auto matched = at::empty({n_req, 64},
+                           at::TensorOptions().dtype(at::kInt).device(keys.device()));
+  if (n_req == 0) return matched;
+  unsigned bucket_mask = (unsigned)(keys.size(0) / PREFIX_SLOTS - 1);
+  hipLaunchKernelGGL(prefix_match_kernel, dim3((unsigned)((n_req + 3) / 4)), dim3(256), 0,
+                     current_stream(), keys.data_ptr<int64_t>(), masks.data_ptr<int64_t>(),
+                     stamps.data_ptr<int32_t>(), bucket_mask, hashes.data_ptr<int64_t>(),
+                     n_blocks.data_ptr<int32_t>(), (int)n_req, (int)hashes.size(1),
+                     (pfx_u64)live_mask, (int)now, (int)ttl, matched.data_ptr<int32_t>());
+  return matched;
+}
+
+void prefix_insert(at::Tensor keys, at::Tensor masks, at::Tensor stamps,
+                   at::Tensor counters, at::Tensor hashes, at::Tensor n_blocks,
+                   at::Tensor assign, at::Tensor bit_of, int64_t now, int64_t ttl,
+                   int64_t waves) {
+  check_prefix_table(keys, masks, stamps, "prefix_insert");
+  check_prefix_hashes(hashes, n_blocks, keys, "prefix_insert");
+  check_cuda(counters, "counters");
+  check_cuda(assign, "assign");
+  check_cuda(bit_of, "bit_of");
+  TORCH_CHECK(counters.scalar_type() == at::kInt && counters.dim() == 1 &&
+                  counters.size(0) == 4,
+              "prefix_insert: counters must be int32[4]");
+  TORCH_CHECK(assign.scalar_type() == at::kInt && assign.dim() == 1 &&
+                  assign.size(0) == hashes.size(0),
+              "prefix_insert: assign must be int32[n_req]");
+  TORCH_CHECK(bit_of.scalar_type() == at::kLong && bit_of.dim() == 1,
+              "prefix_insert: bit_of must be int64[n_rep]");
+  TORCH_CHECK(bit_of.size(0) <= 64, "prefix_insert: at most 64 replicas");
+  TORCH_CHECK(counters.device() == keys.device() && assign.device() == keys.device() &&
+                  bit_of.device() == keys.device(),
+              "prefix_insert: all tensors must be on one device");
+  TORCH_CHECK(now >= 0 && now <= INT32_MAX && ttl >= 0 && ttl <= INT32_MAX,
+              "prefix_insert: now and ttl must fit a non-negative int32");
+  long long n_req = hashes.size(0);
+  if (n_req == 0 || bit_of.size(0) == 0) return;
+  long long n_buckets = keys.size(0) / PREFIX_SLOTS;
+  // W = 4 * grid waves share the buckets (bucket % W). The table state does
+  // not depend on W; the default is from profiles/prefix_picker.md.
+  TORCH_CHECK(waves >= 0 && waves <= 4096, "prefix_insert: waves must be in [0, 4096]");
+  if (waves == 0) waves = PREFIX_INSERT_WAVES;
+  unsigned grid = (unsigned)((std::min<long long>(n_buckets, waves) + 3) / 4);
+  hipLaunchKernelGGL(prefix_insert_kernel, dim3(grid), dim3(256), 0, current_stream(),
+                     keys.data_ptr<int64_t>(), masks.data_ptr<int64_t>(),
+                     stamps.data_ptr<int32_t>(), (unsigned)(n_buckets - 1),
+                     counters.data_ptr<int32_t>(), hashes.data_ptr<int64_t>(),
+                     n_blocks.data_ptr<int32_t>(), assign.data_ptr<int32_t>(),
+                     bit_of.data_ptr<int64_t>(), (int)bit_of.size(0), (int)n_req,
+                     (int)hashes.size(1), (int)now, (int)ttl);
+}
+
+void prefix_clear_bits(at::Tensor masks, int64_t mask) {
+  check_cuda(masks, "masks");
+  TORCH_CHECK(masks.scalar_type() == at::kLong && masks.dim() == 1,
+              "prefix_clear_bits: masks must be int64[n_buckets*16]");
+  long long n = masks.numel();
+  if (n == 0 || mask == 0) return;
+  unsigned grid = (unsigned)std::min<long long>((n + 255) / 256, 2048);
+  hipLaunchKernelGGL(prefix_clear_bits_kernel, dim3(grid), dim3(256), 0, current_stream(),
+                     masks.data_ptr<int64_t>(), n, (long long)~mask);
+}
+
+at::Tensor kv_score_assign_prefix(at::Tensor stats, at::Tensor pred_tokens,
+                                  at::Tensor matched, int64_t block_tokens, double w_kv,
+                                  double w_q, double w_a, double w_p) {
+  check_cuda(stats, "stats");
+  check_cuda(pred_tokens, "pred_tokens");
+  check_cuda(matched, "matched");
+  TORCH_CHECK(stats.scalar_type() == at::kFloat && stats.dim() == 2 && stats.size(1) == 4,
+              "kv_score_assign_prefix: stats must be float32[n_rep, 4]");
+  TORCH_CHECK(pred_tokens.scalar_type() == at::kFloat && pred_tokens.dim() == 1,
+              "kv_score_assign_prefix: pred_tokens must be float32[n_req]");
+  int n_rep = (int)stats.size(0);
+  TORCH_CHECK(n_rep <= 64, "at most 64 replicas");
+  long long n_req = pred_tokens.numel();
+  TORCH_CHECK(matched.scalar_type() == at::kInt && matched.dim() == 2 &&
+                  matched.size(0) == n_req && matched.size(1) >= n_rep,
+              "kv_score_assign_prefix: matched must be int32[n_req, >= n_rep]");
+  TORCH_CHECK(block_tokens == 8 || block_tokens == 16 || block_tokens == 32 ||
+                  block_tokens == 64,
+              "kv_score_assign_prefix: block_tokens must be 8, 16, 32 or 64");
+  TORCH_CHECK(pred_tokens.device() == stats.device() && matched.device() == stats.device(),
+              "kv_score_assign_prefix: all tensors must be on one device");
+  auto assign = at::empty({n_req},
+                          at::TensorOptions().dtype(at::kInt).device(stats.device()));
+  if (n_req == 0) return assign;
+  hipLaunchKernelGGL(kv_scorer_prefix_kernel, dim3(1), dim3(64), 0, current_stream(),
+                     stats.data_ptr<float>(), n_rep, pred_tokens.data_ptr<float>(),
+                     (int)n_req, matched.data_ptr<int32_t>(), (int)matched.size(1),
+                     (int)block_tokens, (float)w_kv, (float)w_q, (float)w_a, (float)w_p,
+                     assign.data_ptr<int32_t>());
+  return assign;
+}
+
 // MFMA layout probe: C = A(16x32) @ B(32x16) as one intrinsic call; used by
 // the HW test to verify the documented fragment layouts against torch.
 __global__ void mfma_probe_kernel(const bf16* __restrict__ A, const bf16* __restrict__ Bt,
@@ -550,5 +737,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "aligned (the kernel reads 4 row tags as 16-byte vectors): pass "
         "tensors sliced from row 4k of their allocation, not e.g. row_scope[1:].");
   m.def("kv_score_assign", &kv_score_assign, "greedy KV-occupancy assignment");
+  m.def("prefix_block_hashes", &prefix_block_hashes,
+        "chained token-block hashes per request: (hashes int64[n_req, max_blocks], "
+        "n_blocks int32[n_req]); semantics in aigw/ops/prefix_ref.py");
+  m.def("prefix_match", &prefix_match,
+        "per request and replica bit, the leading run of blocks the index holds "
+        "for that bit: int32[n_req, 64]");
+  m.def("prefix_insert", &prefix_insert,
+        "apply (hash, replica bit) entries to the index in list order per bucket; "
+        "waves (0 = default) sets how many waves share the buckets and never "
+        "changes the result",
+        py::arg("keys"), py::arg("masks"), py::arg("stamps"), py::arg("counters"),
+        py::arg("hashes"), py::arg("n_blocks"), py::arg("assign"), py::arg("bit_of"),
+        py::arg("now"), py::arg("ttl"), py::arg("waves") = 0);
+  m.def("prefix_clear_bits", &prefix_clear_bits, "masks &= ~mask over the whole table");
+  m.def("kv_score_assign_prefix", &kv_score_assign_prefix,
+        "greedy KV-occupancy assignment with a prefix-hit term");
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
 }

@@ -630,9 +630,10 @@ cache_topk_scoped_kernel_t(const typename E::elem* __restrict__ index, long long
 // ---------------------------------------------------------------------------
 // 4. KV-occupancy endpoint scorer: greedy sequential assignment of a request
 //    batch to replicas. One wave; lane = replica. score = w_kv*(free KV frac
-//    after assignment) - w_q*queue_depth - w_a*active. Mirrors the EPP
-//    "prefix-cache + queue depth" scoring the reference delegates to an
-//    external endpoint-picker service.
+//    after assignment) - w_q*queue_depth - w_a*active. Mirrors the EPP's
+//    queue and KV-cache-utilization scorers, which the reference delegates
+//    to an external endpoint-picker service. It never looks at the prompt:
+//    the prefix-cache scorer is kv_scorer_prefix_kernel (prefix_kernels.cuh).
 // ---------------------------------------------------------------------------
 
 __global__ void kv_scorer_kernel(const float* __restrict__ stats,  // R x 4
