@@ -102,6 +102,22 @@ async def _run_shard(args, rank: int = 0, world: int = 1) -> None:
         strict_schema=getattr(args, "strict_schema", False),
     )
 
+    # the shard primary owns the prefix indexes (RemoteGPUClient workers RPC
+    # to it), and is also where StateSync runs
+    prefix_owner = gpu_services if hasattr(gpu_services, "prefix_prepare") else None
+
+    def _prepare_prefix(config) -> None:
+        """Build the index of every prefixCache.replicate route now: rows
+        of other shards may arrive before the route's first local pick."""
+        if prefix_owner is None:
+            return
+        for route in config.routes:
+            pc = route.prefix_cache
+            if pc is not None and pc.replicate:
+                prefix_owner.prefix_prepare(route.name, pc.settings())
+
+    _prepare_prefix(cfg)
+
     sync = None
     if world > 1:
         import torch.distributed as dist
@@ -109,11 +125,11 @@ async def _run_shard(args, rank: int = 0, world: int = 1) -> None:
         if dist.is_initialized():  # primary process of each shard only
             from aigw.parallel import StateSync
 
-            sync = StateSync(server.limiter)
+            sync = StateSync(server.limiter, prefix=prefix_owner)
             await sync.start()
 
     watcher = None
-    reload_cbs = [server.swap_runtime]
+    reload_cbs = [server.swap_runtime, lambda rc: _prepare_prefix(rc.config)]
 
     def _on_reload(rc):
         for cb in reload_cbs:

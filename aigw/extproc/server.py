@@ -22,7 +22,6 @@ dropped on streamed responses.
 from __future__ import annotations
 
 import asyncio
-import dataclasses
 import json
 import logging
 import time
@@ -798,7 +797,7 @@ class GatewayServer:
                     pick = await self.gpu.pick_endpoint_prefix(
                         route.route.name, [b.name for b in tier0], stats_rows,
                         chat_text, float(gpu_input_tokens or 256),
-                        settings=dataclasses.asdict(pc),
+                        settings=pc.settings(),
                     )
                     if not 0 <= pick < len(tier0):
                         raise ValueError(f"prefix pick {pick} out of range")

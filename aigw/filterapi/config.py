@@ -18,6 +18,7 @@ counters — SURVEY.md §5.8).
 
 from __future__ import annotations
 
+import dataclasses
 import enum
 from dataclasses import dataclass, field
 from typing import Optional
@@ -324,6 +325,18 @@ class PrefixCache:
     buckets: int = 65536  # index buckets of 16 slots; a power of two
     ttl_s: float = 300.0  # seconds an index entry stays live (a guess)
     weight: float = 1.0  # score weight of the matched fraction (a guess)
+    # ship index inserts to the node's other shards on the state-sync tick,
+    # so a follow-up turn finds its prefix whichever shard it lands on
+    replicate: bool = False
+
+    def settings(self) -> dict:
+        """The ``settings`` GPUServices builds the route's index from. The
+        replicate key is only there when it is on, so a route without it
+        hands over exactly what it did before the key existed."""
+        s = dataclasses.asdict(self)
+        if not s["replicate"]:
+            del s["replicate"]
+        return s
 
 
 @dataclass
@@ -580,6 +593,8 @@ def _parse_prefix_cache(d, ctx) -> PrefixCache:
         raise ConfigError(f"{ctx}: ttlS must be positive")
     if not _num(pc.weight) or not pc.weight >= 0:
         raise ConfigError(f"{ctx}: weight must not be negative")
+    if not isinstance(pc.replicate, bool):
+        raise ConfigError(f"{ctx}: replicate must be true or false")
     return pc
 
 

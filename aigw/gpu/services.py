@@ -121,6 +121,7 @@ class GPUServices:
         # core-constrained deployments.
         self.async_counts = _os.environ.get("AIGW_GPU_ASYNC_PATH", "") == "1"
         self._prefix: dict = {}  # pool name -> PrefixIndex, built lazily
+        self.prefix_rows_dropped = 0  # replicated rows of pools not built here
         self._pending: list[_Pending] = []
         self._pending_texts = 0
         self._flush_handle = None
@@ -347,6 +348,7 @@ class GPUServices:
                 buckets=int(s.get("buckets", 65536)),
                 ttl_s=s.get("ttl_s", 300.0),
                 weight=float(s.get("weight", 1.0)),
+                replicate=bool(s.get("replicate", False)),
                 device=self.device,
                 _hip=self.tokenizer.hip,
             )
@@ -399,6 +401,56 @@ class GPUServices:
 
     def prefix_stats(self) -> dict:
         return {pool: idx.stats() for pool, idx in self._prefix.items()}
+
+    # ---- prefix index replication (driven by StateSync, which runs on its
+    #      own thread: every index is touched on the GPU executor only) -------
+
+    def prefix_prepare(self, pool: str, settings: Optional[dict] = None) -> None:
+        """Build the pool's index now, not on its first pick, so that rows
+        other shards send for it have somewhere to go from the start."""
+        self._executor.submit(self._prefix_index, pool, settings).result()
+
+    def _prefix_drain(self, max_n: int) -> torch.Tensor:
+        parts, left = [], int(max_n)
+        for idx in self._prefix.values():
+            if not idx.replicate or left <= 0:
+                continue
+            rec = idx.drain_log(left)
+            if rec.shape[0]:
+                salt = torch.full((rec.shape[0], 1), idx.salt, dtype=torch.int64,
+                                  device=rec.device)
+                parts.append(torch.cat([rec, salt], dim=1))
+                left -= rec.shape[0]
+        if not parts:
+            return torch.zeros(0, 3, dtype=torch.int64, device=self.device)
+        return torch.cat(parts)
+
+    def prefix_drain_sync(self, max_n: int) -> torch.Tensor:
+        """Blocking: the oldest <= max_n replication records over all
+        replicating pools, as int64[k, 3] rows of (hash, member key,
+        salt_of(pool)) on the device."""
+        return self._executor.submit(self._prefix_drain, max_n).result()
+
+    def _prefix_apply(self, rows: torch.Tensor) -> None:
+        rows = rows.to(self.device, torch.int64)
+        if rows.shape[0] == 0:
+            return
+        by_salt = {idx.salt: idx for idx in self._prefix.values() if idx.replicate}
+        done = 0
+        for salt in torch.unique(rows[:, 2]).cpu().tolist():
+            idx = by_salt.get(salt)
+            if idx is None:
+                continue
+            rec = rows[rows[:, 2] == salt][:, :2].contiguous()  # keeps list order
+            idx.apply_remote(rec)
+            done += rec.shape[0]
+        self.prefix_rows_dropped += rows.shape[0] - done
+
+    def prefix_apply_sync(self, rows: torch.Tensor) -> None:
+        """Blocking: apply another shard's drained rows, routed by salt.
+        Rows of a pool that is not built (or not replicating) here are
+        dropped and counted in ``prefix_rows_dropped``."""
+        self._executor.submit(self._prefix_apply, rows).result()
 
     async def assign_replicas(self, stats: torch.Tensor, predicted: torch.Tensor):
         loop = asyncio.get_running_loop()

@@ -221,6 +221,57 @@ class PrefixTable:
     def clear_bits(self, mask: int) -> None:
         self.masks &= np.int64(to_i64(~to_u64(mask)))
 
+    def export(self, entries, now: int, ttl: int, refresh: int) -> list[tuple[int, int]]:
+        """The entries of an insert list that other shards need to hear of,
+        judged against the table as it stands BEFORE the list is applied.
+        With s the slot of bucket(h) whose key is h, (h, bit) is exported
+        iff there is no such slot, or s is not live, or masks[s] lacks bit,
+        or now - stamps[s] >= refresh (the origin re-announces an entry it
+        keeps refreshing, or it would expire elsewhere while still hot).
+        Input order is kept, duplicates included: applying is idempotent."""
+        out = []
+        for h, bit in entries:
+            base = self.bucket(h) * SLOTS
+            s = next((s for s in range(base, base + SLOTS) if self.keys[s] == h), None)
+            if (s is None or not self.live(s, now, ttl)
+                    or to_u64(self.masks[s]) & to_u64(bit) == 0
+                    or int(now) - int(self.stamps[s]) >= int(refresh)):
+                out.append((h, bit))
+        return out
+
+
+def member_key(name) -> int:
+    """uint64 identity of a pool member on every shard: the first 8 bytes
+    of the SHA-256 of its name, 0 remapped to 1. Shards hand out replica
+    bits in their own order; the key is what travels."""
+    if isinstance(name, str):
+        name = name.encode("utf-8")
+    return int.from_bytes(hashlib.sha256(bytes(name)).digest()[:8], "little") or 1
+
+
+def refresh_of(ttl: int) -> int:
+    """Age at which the origin exports a live entry again: half its TTL."""
+    return NEVER if ttl == NEVER else max(int(ttl) // 2, 1)
+
+
+def apply_remote(table: PrefixTable, records, bit_of_key: dict, now: int,
+                 ttl: int) -> tuple[int, int]:
+    """Apply another shard's exported (h, member_key) records: (applied,
+    skipped). A record with h == 0 or a key this shard does not know is
+    skipped; the rest go through PrefixTable.apply in list order under the
+    receiver's own ``now`` (stamps never travel: every index has its own
+    clock). Keys are compared as uint64 bit patterns."""
+    known = {to_u64(k): b for k, b in bit_of_key.items()}
+    entries, skipped = [], 0
+    for h, key in records:
+        bit = known.get(to_u64(key))
+        if int(h) == 0 or bit is None:
+            skipped += 1
+            continue
+        entries.append((to_i64(int(h)), to_i64(int(bit))))
+    table.apply(entries, now, ttl)
+    return len(entries), skipped
+
 
 def score_assign(stats, pred, matched, block_tokens: int, weights, dtype=np.float32):
     """Greedy assignment with the prefix-hit term, evaluated in ``dtype``.

@@ -8,6 +8,11 @@ is then recorded in the table. Semantics: aigw/ops/prefix_ref.py.
 
 A batch is matched before any of its own inserts, so two new same-prefix
 requests of one batch do not attract each other.
+
+With ``replicate=True`` the index also logs, on the device, the inserts
+the node's other shards need to hear of, as (hash, member key) records: a
+member's key is the same on every shard, its bit is not. StateSync drains
+the log on its tick and applies the other shards' records here.
 """
 
 from __future__ import annotations
@@ -19,10 +24,12 @@ import torch
 
 from aigw.ops import load_hip_module
 from aigw.ops.prefix_ref import (
-    BLOCK_TOKENS, MAX_BLOCKS, N_BITS, NEVER, SLOTS, salt_of, to_i64,
+    BLOCK_TOKENS, MAX_BLOCKS, N_BITS, NEVER, SLOTS, member_key, refresh_of, salt_of,
+    to_i64,
 )
 
 SCORE_WEIGHTS = (1.0, 0.1, 0.05)  # w_kv, w_q, w_a of pick_endpoint
+LOG_RECORDS = 65536  # replication log rows of (hash, member key): 1 MiB
 
 
 class PrefixIndex:
@@ -35,6 +42,7 @@ class PrefixIndex:
         buckets: int = 65536,
         ttl_s: Optional[float] = 300.0,  # None: entries never expire
         weight: float = 1.0,
+        replicate: bool = False,  # log inserts for the other shards
         device: str = "cuda",
         _hip=None,
         _clock=time.monotonic,
@@ -76,6 +84,20 @@ class PrefixIndex:
         # device copies of the last member list's bits (pools change rarely)
         self._dev_key: Optional[tuple] = None
         self._dev_cols = self._dev_bit_of = None
+        # replication: the batch's entries that other shards need are
+        # appended on the device as (hash, member key) rows; drain_log()
+        # hands them to the state-sync tick, apply_remote() takes theirs
+        self.replicate = bool(replicate)
+        self.refresh = refresh_of(self.ttl)
+        self.repl_counters = torch.zeros(4, dtype=torch.int32, device=self.device)
+        self.log = self.log_n = None
+        if self.replicate:
+            self.log = torch.zeros(LOG_RECORDS, 2, dtype=torch.int64, device=self.device)
+            self.log_n = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._dev_names: Optional[tuple] = None
+        self._dev_key_of = None
+        self._dev_members: Optional[tuple] = None
+        self._dev_member_keys = self._dev_member_bits = None
 
     def now(self) -> int:
         return int(min(max(self._clock() - self._t0, 0.0), NEVER - 1))
@@ -156,11 +178,71 @@ class PrefixIndex:
     def clear_bits(self, mask: int) -> None:
         self.hip.prefix_clear_bits(self.masks, mask)
 
+    # ---- replication -----------------------------------------------------
+
+    def _dev_keys(self, members: Sequence[str]) -> torch.Tensor:
+        """member_key of each member, in ``members`` (stats row) order."""
+        names = tuple(members)
+        if names != self._dev_names:
+            self._dev_key_of = torch.tensor([to_i64(member_key(m)) for m in names],
+                                            dtype=torch.int64, device=self.device)
+            self._dev_names = names
+        return self._dev_key_of
+
+    def export(self, hashes: torch.Tensor, n_blocks: torch.Tensor, assign: torch.Tensor,
+               members: Sequence[str], bits: Sequence[int],
+               now: Optional[int] = None) -> None:
+        """Append the batch's entries that other shards need to hear of to
+        the log; to be called before insert() of the same batch. No host
+        sync."""
+        if not self.replicate:
+            raise RuntimeError("PrefixIndex was built with replicate=False")
+        self.hip.prefix_export(
+            self.keys, self.masks, self.stamps, hashes, n_blocks, assign,
+            self._dev_bits(bits)[1], self._dev_keys(members), self.log, self.log_n,
+            self.repl_counters, self.now() if now is None else now, self.ttl, self.refresh,
+        )
+
+    def drain_log(self, max_n: int) -> torch.Tensor:
+        """The oldest <= max_n log records as int64[k, 2] rows of (hash,
+        member key) on the device; the rest stay, in FIFO order. The only
+        place that reads log_n on the host: one sync per tick, off the
+        request path."""
+        if not self.replicate:
+            return torch.zeros(0, 2, dtype=torch.int64, device=self.device)
+        n = int(self.log_n.item())
+        k = max(min(n, int(max_n)), 0)
+        out = self.log[:k].clone()
+        if k:
+            if k < n:
+                self.log[: n - k] = self.log[k:n].clone()
+            self.log_n.fill_(n - k)
+        return out
+
+    def apply_remote(self, rec: torch.Tensor, now: Optional[int] = None) -> None:
+        """Apply another shard's drained records under this index's own
+        bits and clock. Records of members unknown here are skipped."""
+        rec = rec.to(self.device, torch.int64).contiguous()
+        live = tuple(sorted(self._bit.items(), key=lambda nb: nb[1]))
+        if live != self._dev_members:
+            self._dev_member_keys = torch.tensor(
+                [to_i64(member_key(name)) for name, _ in live],
+                dtype=torch.int64, device=self.device)
+            self._dev_member_bits = torch.tensor(
+                [to_i64(1 << b) for _, b in live], dtype=torch.int64, device=self.device)
+            self._dev_members = live
+        self.hip.prefix_apply_remote(
+            self.keys, self.masks, self.stamps, self.counters, rec, rec.shape[0],
+            self._dev_member_keys, self._dev_member_bits, self.repl_counters,
+            self.now() if now is None else now, self.ttl,
+        )
+
     def assign(self, members: Sequence[str], stats: torch.Tensor,
                predicted: torch.Tensor, out_ids: torch.Tensor,
                req_off: torch.Tensor, n_bytes: int):
-        """hash -> match -> score -> insert for one batch, all on the
-        current stream with no host sync. Returns device tensors
+        """hash -> match -> score -> (export, when replicating) -> insert
+        for one batch, all on the current stream with no host sync.
+        Returns device tensors
         (assign int32[n_req], hit_blocks int32[n_req], n_blocks): hit_blocks
         is the matched run on the replica each request went to."""
         bits = self.set_members(members)
@@ -173,13 +255,17 @@ class PrefixIndex:
         assign = self.hip.kv_score_assign_prefix(
             stats, predicted, by_lane, self.block_tokens, w_kv, w_q, w_a, self.weight
         )
+        if self.replicate:  # judged against the table before this batch's inserts
+            self.export(hashes, n_blocks, assign, members, bits, now)
         self.insert(hashes, n_blocks, assign, bits, now)
         hit = by_lane.gather(1, assign.to(torch.int64).unsqueeze(1)).squeeze(1)
         return assign, hit, n_blocks
 
     def stats(self) -> dict:
         c = self.counters.cpu().tolist()
+        r = self.repl_counters.cpu().tolist()
         return {
             "inserted": c[0], "refreshed": c[1], "reused_expired": c[2],
             "evicted_live": c[3], "members": len(self._bit),
+            "exported": r[0], "dropped": r[1], "applied": r[2], "skipped": r[3],
         }

@@ -44,6 +44,7 @@ class StateSync:
         self,
         limiter,
         cache=None,
+        prefix=None,
         *,
         interval_s: float = 0.25,
         device: Optional[torch.device] = None,
@@ -53,6 +54,9 @@ class StateSync:
             raise RuntimeError("torch.distributed must be initialized for StateSync")
         self.limiter = limiter
         self.cache = cache
+        # prefix-index replication: an object with prefix_drain_sync(max_n)
+        # and prefix_apply_sync(rows) (GPUServices)
+        self.prefix = prefix
         self.interval_s = interval_s
         self.group = group
         backend = dist.get_backend(group)
@@ -83,6 +87,8 @@ class StateSync:
         dist.all_reduce(self._buf, op=dist.ReduceOp.SUM, group=self.group)
         if self.cache is not None:
             self._sync_cache()
+        if self.prefix is not None:
+            self._sync_prefix()
         nonzero = torch.nonzero(self._buf, as_tuple=False).flatten()
         if nonzero.numel():
             host = self._buf[nonzero].cpu().tolist()
@@ -174,6 +180,40 @@ class StateSync:
                     cache.insert_remote(rows[i], value, scope=scope, ttl_s=None)
                 elif ttl_s > 0:
                     cache.insert_remote(rows[i], value, scope=scope, ttl_s=ttl_s)
+
+    # ---- prefix block index replication ---------------------------------------
+
+    MAX_PREFIX_RECORDS_PER_TICK = 16384
+
+    def _sync_prefix(self) -> None:
+        """All-gather the prefix-index inserts each shard logged since the
+        last tick, so a follow-up turn finds its prefix on whichever shard
+        it lands. A record is an int64 row (block hash, member key, pool
+        salt): identities every shard agrees on; replica bits and stamps
+        are local and never travel. Fixed sequence per tick, so shards stay
+        aligned when some have nothing to send: one all-gather of the
+        record count, then, when any count is non-zero, one all-gather of
+        the zero-padded int64[max_k, 3] block. Received blocks are applied
+        in ascending rank order; the own rank's block is skipped. What
+        exceeds the per-tick cap stays in the sender's log for the next."""
+        rank = dist.get_rank(self.group)
+        world = dist.get_world_size(self.group)
+        rows = self.prefix.prefix_drain_sync(self.MAX_PREFIX_RECORDS_PER_TICK)
+        rows = rows.to(self.device, torch.int64).reshape(-1, 3)
+        count = torch.tensor([rows.shape[0]], dtype=torch.int64, device=self.device)
+        all_counts = [torch.zeros_like(count) for _ in range(world)]
+        dist.all_gather(all_counts, count, group=self.group)
+        counts = [int(c[0]) for c in all_counts]
+        max_k = max(counts)
+        if max_k == 0:
+            return
+        pad = torch.zeros(max_k, 3, dtype=torch.int64, device=self.device)
+        pad[: rows.shape[0]] = rows
+        blocks = [torch.zeros_like(pad) for _ in range(world)]
+        dist.all_gather(blocks, pad, group=self.group)
+        for r in range(world):
+            if r != rank and counts[r]:
+                self.prefix.prefix_apply_sync(blocks[r][: counts[r]])
 
     # ---- background loop -----------------------------------------------------
 

@@ -651,6 +651,126 @@ void prefix_insert(at::Tensor keys, at::Tensor masks, at::Tensor stamps,
                      (int)hashes.size(1), (int)now, (int)ttl);
 }
 
+#define PREFIX_EXPORT_MAX_GROUPS 1024
+
+static void check_repl_counters(const at::Tensor& repl_counters, const at::Tensor& table,
+                                const char* who) {
+  check_cuda(repl_counters, "repl_counters");
+  TORCH_CHECK(repl_counters.scalar_type() == at::kInt && repl_counters.dim() == 1 &&
+                  repl_counters.size(0) == 4,
+              who, ": repl_counters must be int32[4]");
+  TORCH_CHECK(repl_counters.device() == table.device(), who,
+              ": all tensors must be on one device");
+}
+
+void prefix_export(at::Tensor keys, at::Tensor masks, at::Tensor stamps, at::Tensor hashes,
+                   at::Tensor n_blocks, at::Tensor assign, at::Tensor bit_of,
+                   at::Tensor key_of, at::Tensor log, at::Tensor log_n,
+                   at::Tensor repl_counters, int64_t now, int64_t ttl, int64_t refresh) {
+  check_prefix_table(keys, masks, stamps, "prefix_export");
+  check_prefix_hashes(hashes, n_blocks, keys, "prefix_export");
+  check_cuda(assign, "assign");
+  check_cuda(bit_of, "bit_of");
+  check_cuda(key_of, "key_of");
+  check_cuda(log, "log");
+  check_cuda(log_n, "log_n");
+  check_repl_counters(repl_counters, keys, "prefix_export");
+  TORCH_CHECK(assign.scalar_type() == at::kInt && assign.dim() == 1 &&
+                  assign.size(0) == hashes.size(0),
+              "prefix_export: assign must be int32[n_req]");
+  TORCH_CHECK(bit_of.scalar_type() == at::kLong && bit_of.dim() == 1,
+              "prefix_export: bit_of must be int64[n_rep]");
+  TORCH_CHECK(bit_of.size(0) <= 64, "prefix_export: at most 64 replicas");
+  TORCH_CHECK(key_of.scalar_type() == at::kLong && key_of.dim() == 1 &&
+                  key_of.size(0) == bit_of.size(0),
+              "prefix_export: key_of must be int64[n_rep]");
+  TORCH_CHECK(log.scalar_type() == at::kLong && log.dim() == 2 && log.size(1) == 2 &&
+                  log.size(0) <= INT32_MAX,
+              "prefix_export: log must be int64[cap, 2]");
+  TORCH_CHECK(log_n.scalar_type() == at::kInt && log_n.dim() == 1 && log_n.size(0) == 1,
+              "prefix_export: log_n must be int32[1]");
+  TORCH_CHECK(assign.device() == keys.device() && bit_of.device() == keys.device() &&
+                  key_of.device() == keys.device() && log.device() == keys.device() &&
+                  log_n.device() == keys.device(),
+              "prefix_export: all tensors must be on one device");
+  TORCH_CHECK(now >= 0 && now <= INT32_MAX && ttl >= 0 && ttl <= INT32_MAX &&
+                  refresh >= 0 && refresh <= INT32_MAX,
+              "prefix_export: now, ttl and refresh must fit a non-negative int32");
+  long long n_req = hashes.size(0);
+  if (n_req == 0 || bit_of.size(0) == 0) return;
+  // scratch from the caching allocator (no sync, no kernel), as the outputs
+  // of prefix_match and prefix_block_hashes are
+  auto flag_words = at::empty({n_req, PREFIX_MAX_BLOCKS / 64},
+                              at::TensorOptions().dtype(at::kLong).device(keys.device()));
+  auto counts = at::empty({n_req + 1},
+                          at::TensorOptions().dtype(at::kInt).device(keys.device()));
+  unsigned bucket_mask = (unsigned)(keys.size(0) / PREFIX_SLOTS - 1);
+  hipLaunchKernelGGL(prefix_export_flag_kernel, dim3((unsigned)((n_req + 3) / 4)), dim3(256),
+                     0, current_stream(), keys.data_ptr<int64_t>(),
+                     masks.data_ptr<int64_t>(), stamps.data_ptr<int32_t>(), bucket_mask,
+                     hashes.data_ptr<int64_t>(), n_blocks.data_ptr<int32_t>(),
+                     assign.data_ptr<int32_t>(), bit_of.data_ptr<int64_t>(),
+                     (int)bit_of.size(0), (int)n_req, (int)hashes.size(1), (int)now, (int)ttl,
+                     (int)refresh, log_n.data_ptr<int32_t>(),
+                     reinterpret_cast<pfx_u64*>(flag_words.data_ptr<int64_t>()),
+                     counts.data_ptr<int32_t>());
+  // a workgroup writes 4 requests at a time; past 4 * 1024 workgroups' worth
+  // each takes more groups, so the bases cost at most 1024 passes over counts
+  long long groups = (n_req + 3) / 4;
+  long long per = 4 * ((groups + PREFIX_EXPORT_MAX_GROUPS - 1) / PREFIX_EXPORT_MAX_GROUPS);
+  unsigned grid = (unsigned)((n_req + per - 1) / per);
+  hipLaunchKernelGGL(prefix_export_write_kernel, dim3(grid), dim3(256), 0, current_stream(),
+                     hashes.data_ptr<int64_t>(), assign.data_ptr<int32_t>(),
+                     key_of.data_ptr<int64_t>(), (int)n_req, (int)hashes.size(1), (int)per,
+                     reinterpret_cast<const pfx_u64*>(flag_words.data_ptr<int64_t>()),
+                     counts.data_ptr<int32_t>(), log.data_ptr<int64_t>(),
+                     (long long)log.size(0), log_n.data_ptr<int32_t>(),
+                     repl_counters.data_ptr<int32_t>());
+}
+
+void prefix_apply_remote(at::Tensor keys, at::Tensor masks, at::Tensor stamps,
+                         at::Tensor counters, at::Tensor rec, int64_t n_rec,
+                         at::Tensor member_keys, at::Tensor member_bits,
+                         at::Tensor repl_counters, int64_t now, int64_t ttl, int64_t waves) {
+  check_prefix_table(keys, masks, stamps, "prefix_apply_remote");
+  check_cuda(counters, "counters");
+  check_cuda(rec, "rec");
+  check_cuda(member_keys, "member_keys");
+  check_cuda(member_bits, "member_bits");
+  check_repl_counters(repl_counters, keys, "prefix_apply_remote");
+  TORCH_CHECK(counters.scalar_type() == at::kInt && counters.dim() == 1 &&
+                  counters.size(0) == 4,
+              "prefix_apply_remote: counters must be int32[4]");
+  TORCH_CHECK(rec.scalar_type() == at::kLong && rec.dim() == 2 && rec.size(1) == 2,
+              "prefix_apply_remote: rec must be int64[n, 2]");
+  TORCH_CHECK(n_rec >= 0 && n_rec <= rec.size(0),
+              "prefix_apply_remote: n_rec must be in [0, rec.size(0)]");
+  TORCH_CHECK(member_keys.scalar_type() == at::kLong && member_keys.dim() == 1,
+              "prefix_apply_remote: member_keys must be int64[n_rep]");
+  TORCH_CHECK(member_keys.size(0) <= 64, "prefix_apply_remote: at most 64 replicas");
+  TORCH_CHECK(member_bits.scalar_type() == at::kLong && member_bits.dim() == 1 &&
+                  member_bits.size(0) == member_keys.size(0),
+              "prefix_apply_remote: member_bits must be int64[n_rep]");
+  TORCH_CHECK(counters.device() == keys.device() && rec.device() == keys.device() &&
+                  member_keys.device() == keys.device() &&
+                  member_bits.device() == keys.device(),
+              "prefix_apply_remote: all tensors must be on one device");
+  TORCH_CHECK(now >= 0 && now <= INT32_MAX && ttl >= 0 && ttl <= INT32_MAX,
+              "prefix_apply_remote: now and ttl must fit a non-negative int32");
+  TORCH_CHECK(waves >= 0 && waves <= 4096, "prefix_apply_remote: waves must be in [0, 4096]");
+  if (n_rec == 0) return;
+  long long n_buckets = keys.size(0) / PREFIX_SLOTS;
+  if (waves == 0) waves = PREFIX_INSERT_WAVES;  // as prefix_insert: never changes the result
+  unsigned grid = (unsigned)((std::min<long long>(n_buckets, waves) + 3) / 4);
+  hipLaunchKernelGGL(prefix_apply_remote_kernel, dim3(grid), dim3(256), 0, current_stream(),
+                     keys.data_ptr<int64_t>(), masks.data_ptr<int64_t>(),
+                     stamps.data_ptr<int32_t>(), (unsigned)(n_buckets - 1),
+                     counters.data_ptr<int32_t>(), rec.data_ptr<int64_t>(),
+                     (long long)n_rec, member_keys.data_ptr<int64_t>(),
+                     member_bits.data_ptr<int64_t>(), (int)member_keys.size(0),
+                     repl_counters.data_ptr<int32_t>(), (int)now, (int)ttl);
+}
+
 void prefix_clear_bits(at::Tensor masks, int64_t mask) {
   check_cuda(masks, "masks");
   TORCH_CHECK(masks.scalar_type() == at::kLong && masks.dim() == 1,
@@ -750,6 +870,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("keys"), py::arg("masks"), py::arg("stamps"), py::arg("counters"),
         py::arg("hashes"), py::arg("n_blocks"), py::arg("assign"), py::arg("bit_of"),
         py::arg("now"), py::arg("ttl"), py::arg("waves") = 0);
+  m.def("prefix_export", &prefix_export,
+        "append the entries of one batch's insert list that other shards need to hear "
+        "of, as (hash, member key) rows in list order, to log[log_n...]; run before "
+        "prefix_insert of the same batch. repl_counters: exported, dropped, applied, "
+        "skipped. No host sync.",
+        py::arg("keys"), py::arg("masks"), py::arg("stamps"), py::arg("hashes"),
+        py::arg("n_blocks"), py::arg("assign"), py::arg("bit_of"), py::arg("key_of"),
+        py::arg("log"), py::arg("log_n"), py::arg("repl_counters"), py::arg("now"),
+        py::arg("ttl"), py::arg("refresh"));
+  m.def("prefix_apply_remote", &prefix_apply_remote,
+        "apply (hash, member key) records of another shard in list order per bucket; "
+        "the replica bit is looked up among member_keys; waves as in prefix_insert",
+        py::arg("keys"), py::arg("masks"), py::arg("stamps"), py::arg("counters"),
+        py::arg("rec"), py::arg("n_rec"), py::arg("member_keys"), py::arg("member_bits"),
+        py::arg("repl_counters"), py::arg("now"), py::arg("ttl"), py::arg("waves") = 0);
   m.def("prefix_clear_bits", &prefix_clear_bits, "masks &= ~mask over the whole table");
   m.def("kv_score_assign_prefix", &kv_score_assign_prefix,
         "greedy KV-occupancy assignment with a prefix-hit term");
