@@ -259,6 +259,11 @@ def _check_cache_flags(args) -> None:
             "--semantic-cache-scope index and --semantic-cache-ttl are not "
             "supported by the native front (--front fast) yet: its in-process "
             "cache has no per-row scope or expiry — use --front lean")
+    if (args.front == "fast" and args.gpu and args.semantic_cache
+            and getattr(args, "cache_index_dtype", "bf16") == "mxfp4"):
+        from aigw.extproc.fast_front import MXFP4_NATIVE_FRONT
+
+        raise SystemExit(MXFP4_NATIVE_FRONT)
 
 
 def cmd_run(args) -> int:
@@ -382,9 +387,12 @@ def main(argv=None) -> int:
                            "CPython's GIL caps one loop near ~3k req/s)")
     runp.add_argument("--gpu", action="store_true", help="enable GPU services")
     runp.add_argument("--semantic-cache", action="store_true")
-    runp.add_argument("--cache-index-dtype", choices=["bf16", "fp8"],
+    runp.add_argument("--cache-index-dtype", choices=["bf16", "fp8", "mxfp4"],
                       default="bf16", dest="cache_index_dtype",
-                      help="semantic-cache index precision (fp8 = 2x rows per GB, faster lookups, ~1%% cosine error)")
+                      help="semantic-cache index precision (fp8 = 2x rows per GB, faster "
+                           "lookups, ~1%% cosine error; mxfp4 = 3.7x rows per GB at "
+                           "dim 384, 4-bit MX blocks against fp8 queries, not served "
+                           "by --front fast)")
     runp.add_argument("--semantic-cache-scope", choices=["value", "index"],
                       default="value", dest="cache_scope",
                       help="where a cached answer's scope (model, route, sampling "

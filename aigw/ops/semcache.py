@@ -21,6 +21,8 @@ from aigw.ops import load_hip_module
 
 NEVER = 0x7FFFFFFF  # row_expiry of a row without a TTL
 
+INDEX_DTYPES = {"bf16": torch.bfloat16, "fp8": torch.float8_e4m3fn, "mxfp4": torch.uint8}
+
 
 def scope_id(b: bytes) -> int:
     """Index scope id of a scope tag: the first 8 bytes of its SHA-256 as a
@@ -45,6 +47,8 @@ class SemanticCache:
         index_dtype: str = "bf16",  # "bf16" | "fp8" (OCP e4m3: half the
         # HBM per row -> 2x rows in the 288 GB budget, 2x lookup bandwidth;
         # ~1% cosine error from 3-bit mantissas averaged over 384 dims)
+        # | "mxfp4" (OCP MX e2m1 blocks against fp8 queries: 208 B per
+        # dim-384 row, 3.7x the rows of bf16; aigw/ops/mxfp4_ref.py)
         _hip=None,
         *,
         scoped: bool = False,  # lookups filter rows by scope inside the kernel
@@ -70,10 +74,27 @@ class SemanticCache:
             .to(torch.bfloat16)
             .to(self.device)
         )
-        self.index_dtype = (
-            torch.float8_e4m3fn if index_dtype == "fp8" else torch.bfloat16
-        )
-        self.index = torch.zeros(capacity, dim, dtype=self.index_dtype, device=self.device)
+        if index_dtype not in INDEX_DTYPES:
+            raise ValueError(
+                f"index_dtype must be one of {', '.join(INDEX_DTYPES)}, got {index_dtype!r}")
+        self.mxfp4 = index_dtype == "mxfp4"
+        # dtype of the stored rows; mxfp4 rows are packed nibbles
+        self.index_dtype = INDEX_DTYPES[index_dtype]
+        # dtype the lookup kernels take queries in
+        self.query_dtype = torch.float8_e4m3fn if self.mxfp4 else self.index_dtype
+        if self.mxfp4:
+            if dim % 128 or not 128 <= dim <= 512:
+                raise ValueError(
+                    f"index_dtype='mxfp4' needs dim 128, 256, 384 or 512, got {dim}")
+            self.index = torch.zeros(capacity, dim // 2, dtype=torch.uint8, device=self.device)
+            # one E8M0 scale byte per 32 elements, and 1/|dequantised row|
+            self.index_scale = torch.full((capacity, dim // 32), 127, dtype=torch.uint8,
+                                          device=self.device)
+            self.index_inv_norm = torch.zeros(capacity, dtype=torch.float32,
+                                              device=self.device)
+        else:
+            self.index = torch.zeros(capacity, dim, dtype=self.index_dtype,
+                                     device=self.device)
         # per-row tag read by the scoped lookup kernel (12 B/row): scope id
         # and expiry in whole seconds of the cache's own clock, which
         # starts at 0 when the cache is built
@@ -144,8 +165,16 @@ class SemanticCache:
             now = self.now()
         hi, idx = [], []
         for q0 in range(0, queries.shape[0], 256):  # kernel cap: 256 q/call
-            qs = queries[q0 : q0 + 256].to(self.index_dtype).contiguous()
-            if filtering:
+            qs = queries[q0 : q0 + 256].to(self.query_dtype).contiguous()
+            if self.mxfp4:
+                rows = (view, self.index_scale[: self.size], self.index_inv_norm[: self.size])
+                if filtering:
+                    h, i = self.hip.cache_topk_mxfp4_scoped(
+                        *rows, qs, row_scope, row_expiry, q_scope[q0 : q0 + 256], now
+                    )
+                else:
+                    h, i = self.hip.cache_topk_mxfp4(*rows, qs)
+            elif filtering:
                 h, i = self.hip.cache_topk_scoped(
                     view, qs, row_scope, row_expiry, q_scope[q0 : q0 + 256], now
                 )
@@ -168,7 +197,14 @@ class SemanticCache:
     def _write_row(self, vec: torch.Tensor, response: bytes, scope: int,
                    expiry: int) -> int:
         slot = self.head
-        self.index[slot] = vec
+        if self.mxfp4:
+            packed, scale, inv_norm = self.hip.mxfp4_quantize_rows(
+                vec.to(self.device, torch.bfloat16).reshape(1, self.dim))
+            self.index[slot] = packed[0]
+            self.index_scale[slot] = scale[0]
+            self.index_inv_norm[slot] = inv_norm[0]
+        else:
+            self.index[slot] = vec
         self.row_scope[slot] = scope
         self.row_expiry[slot] = expiry
         self.values[slot] = response
@@ -185,7 +221,8 @@ class SemanticCache:
         cache's default TTL, ``math.inf`` never expires, and a TTL that is
         not positive stores a row no lookup returns."""
         expiry = self._expiry(ttl_s)
-        slot = self._write_row(query_vec.to(self.index_dtype), response, scope, expiry)
+        vec = query_vec if self.mxfp4 else query_vec.to(self.index_dtype)
+        slot = self._write_row(vec, response, scope, expiry)
         if self.record_pending:
             self.pending.append((query_vec.detach(), response, scope, expiry))
         return slot
@@ -193,10 +230,9 @@ class SemanticCache:
     def insert_remote(self, query_vec: torch.Tensor, response: bytes, scope: int = 0,
                       ttl_s: Optional[float] = None) -> int:
         """Insert a row replicated from another shard (never re-pended)."""
-        return self._write_row(
-            query_vec.to(self.index.dtype).to(self.device), response, scope,
-            self._expiry(ttl_s),
-        )
+        # an mxfp4 index quantises the replicated bf16 vector in _write_row
+        vec = query_vec if self.mxfp4 else query_vec.to(self.index.dtype)
+        return self._write_row(vec.to(self.device), response, scope, self._expiry(ttl_s))
 
     def invalidate(self, scope: Optional[int] = None) -> int:
         """Set the expiry of every row of one scope (all rows for None) to

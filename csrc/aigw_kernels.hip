@@ -53,6 +53,12 @@ static inline hipStream_t current_stream() {
 #include "cache_kernels.cuh"
 
 // ---------------------------------------------------------------------------
+// 3c. MXFP4 cache index: row quantiser + block-scaled fp4 x fp8 MFMA lookup
+// ---------------------------------------------------------------------------
+
+#include "mxfp4_kernels.cuh"
+
+// ---------------------------------------------------------------------------
 // 5. Prefix-cache-aware endpoint picking (block hashes, HBM block index)
 // ---------------------------------------------------------------------------
 
@@ -500,6 +506,144 @@ std::vector<at::Tensor> cache_topk_scoped(at::Tensor index, at::Tensor q,
   return {hi, idx};
 }
 
+// MXFP4 index rows from bf16 vectors: (packed u8 [n, dim/2], scale u8
+// [n, dim/32], inv_norm f32 [n]), bit-identical to aigw/ops/mxfp4_ref.py.
+std::vector<at::Tensor> mxfp4_quantize_rows(at::Tensor x) {
+  check_cuda(x, "x");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.dim() == 2,
+              "mxfp4_quantize_rows: bf16 [n, dim] required");
+  long long n = x.size(0);
+  int dim = (int)x.size(1);
+  TORCH_CHECK(dim % 128 == 0 && dim >= 128 && dim <= 512,
+              "mxfp4_quantize_rows: dim must be 128, 256, 384 or 512, got ", dim);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "mxfp4_quantize_rows: x must start 16-byte aligned");
+  auto u8 = at::TensorOptions().dtype(at::kByte).device(x.device());
+  at::Tensor packed = at::empty({n, dim / 2}, u8);
+  at::Tensor scale = at::empty({n, dim / 32}, u8);
+  at::Tensor inv_norm = at::empty({n}, u8.dtype(at::kFloat));
+  if (n == 0) return {packed, scale, inv_norm};
+  hipLaunchKernelGGL(mxfp4_quantize_rows_kernel, dim3((unsigned)((n + 3) / 4)),
+                     dim3(256), 0, current_stream(),
+                     reinterpret_cast<const bf16*>(x.data_ptr<at::BFloat16>()), n, dim,
+                     packed.data_ptr<uint8_t>(), scale.data_ptr<uint8_t>(),
+                     inv_norm.data_ptr<float>());
+  return {packed, scale, inv_norm};
+}
+
+// Checks and launches shared by cache_topk_mxfp4 and cache_topk_mxfp4_scoped
+// (tags == nullptr: unfiltered). n_q <= 256 in two passes of <= 128.
+template <bool SCOPED>
+static std::vector<at::Tensor> cache_topk_mxfp4_impl(
+    const char* op, const at::Tensor& packed, const at::Tensor& scale,
+    const at::Tensor& inv_norm, const at::Tensor& q, const at::Tensor* row_scope,
+    const at::Tensor* row_expiry, const at::Tensor* q_scope, int64_t now) {
+  check_cuda(packed, "packed");
+  check_cuda(scale, "scale");
+  check_cuda(inv_norm, "inv_norm");
+  check_cuda(q, "q");
+  TORCH_CHECK(q.scalar_type() == at::kFloat8_e4m3fn && q.dim() == 2, op,
+              ": q must be float8_e4m3fn [n_q, dim]");
+  long long n_rows = packed.size(0);
+  int n_q = (int)q.size(0), dim = (int)q.size(1);
+  TORCH_CHECK(dim % 128 == 0 && dim >= 128 && dim <= 512, op, ": unsupported dim ", dim,
+              " (supported: 128/256/384/512)");
+  TORCH_CHECK(packed.scalar_type() == at::kByte && packed.dim() == 2 &&
+                  packed.size(1) == dim / 2,
+              op, ": packed must be uint8 [n_rows, dim/2]");
+  TORCH_CHECK(scale.scalar_type() == at::kByte && scale.dim() == 2 &&
+                  scale.size(0) == n_rows && scale.size(1) == dim / 32,
+              op, ": scale must be uint8 [n_rows, dim/32]");
+  TORCH_CHECK(inv_norm.scalar_type() == at::kFloat && inv_norm.dim() == 1 &&
+                  inv_norm.size(0) == n_rows,
+              op, ": inv_norm must be float32 [n_rows]");
+  TORCH_CHECK(n_q <= 256, op, ": at most 256 queries per call");
+  TORCH_CHECK(scale.device() == packed.device() && inv_norm.device() == packed.device() &&
+                  q.device() == packed.device(),
+              op, ": all tensors must be on one device");
+  // 16-byte row and query fragments, a dword of scale bytes per k-step,
+  // 16 bytes of inv_norm per 4 result rows
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(packed.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(scale.data_ptr()) % 4 == 0 &&
+                  reinterpret_cast<uintptr_t>(inv_norm.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              op, ": packed/inv_norm/q must start 16-byte and scale 4-byte aligned");
+  const long long* rs = nullptr;
+  const int* re = nullptr;
+  const long long* qsc = nullptr;
+  if (SCOPED) {
+    check_cuda(*row_scope, "row_scope");
+    check_cuda(*row_expiry, "row_expiry");
+    check_cuda(*q_scope, "q_scope");
+    TORCH_CHECK(row_scope->scalar_type() == at::kLong && row_scope->dim() == 1 &&
+                    row_scope->size(0) == n_rows,
+                "row_scope must be int64[n_rows]");
+    TORCH_CHECK(row_expiry->scalar_type() == at::kInt && row_expiry->dim() == 1 &&
+                    row_expiry->size(0) == n_rows,
+                "row_expiry must be int32[n_rows]");
+    TORCH_CHECK(q_scope->scalar_type() == at::kLong && q_scope->dim() == 1 &&
+                    q_scope->size(0) == n_q,
+                "q_scope must be int64[n_q]");
+    TORCH_CHECK(row_scope->device() == packed.device() &&
+                    row_expiry->device() == packed.device() &&
+                    q_scope->device() == packed.device(),
+                op, ": all tensors must be on one device");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(row_scope->data_ptr()) % 32 == 0 &&
+                    reinterpret_cast<uintptr_t>(row_expiry->data_ptr()) % 16 == 0,
+                "row_scope/row_expiry must start 32/16-byte aligned (row 4k of the "
+                "allocation)");
+    TORCH_CHECK(now >= INT32_MIN && now <= INT32_MAX, "now must fit int32");
+    rs = reinterpret_cast<const long long*>(row_scope->data_ptr<int64_t>());
+    re = row_expiry->data_ptr<int32_t>();
+    qsc = reinterpret_cast<const long long*>(q_scope->data_ptr<int64_t>());
+  }
+  auto best = at::zeros({n_q}, at::TensorOptions().dtype(at::kLong).device(q.device()));
+  if (n_q == 0 || n_rows == 0)
+    return {best, at::full({n_q}, -1, best.options().dtype(at::kInt))};
+  constexpr int ROWTILES = 16;
+  long long blocks = (n_rows + 64 * ROWTILES - 1) / (64 * ROWTILES);
+  auto* best_p = reinterpret_cast<unsigned long long*>(best.data_ptr<int64_t>());
+  auto* q_base = reinterpret_cast<const uint8_t*>(q.data_ptr());
+  auto launch = [&](auto kernel, int q0) {
+    int kq = std::min(128, n_q - q0);
+    // blk_best (+ q_scope stage) + ceil(kq/16)*16 query rows of dim+16 bytes
+    size_t lds_bytes = (SCOPED ? 2 : 1) * 128 * 8 +
+                       (size_t)((kq + 15) / 16 * 16) * (dim + 16);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), lds_bytes,
+                       current_stream(), packed.data_ptr<uint8_t>(),
+                       scale.data_ptr<uint8_t>(), inv_norm.data_ptr<float>(), n_rows,
+                       q_base + (long long)q0 * dim, kq, best_p + q0, rs, re,
+                       SCOPED ? qsc + q0 : nullptr, (int)now);
+  };
+  for (int q0 = 0; q0 < n_q; q0 += 128) {
+    switch (dim >> 7) {
+      case 1: launch(&cache_topk_mxfp4_kernel_t<1, ROWTILES, SCOPED>, q0); break;
+      case 2: launch(&cache_topk_mxfp4_kernel_t<2, ROWTILES, SCOPED>, q0); break;
+      case 3: launch(&cache_topk_mxfp4_kernel_t<3, ROWTILES, SCOPED>, q0); break;
+      default: launch(&cache_topk_mxfp4_kernel_t<4, ROWTILES, SCOPED>, q0); break;
+    }
+  }
+  auto hi = best.bitwise_right_shift(32).to(at::kLong);
+  auto idx = at::where(best == 0, -1, best.bitwise_and(0xFFFFFFFFLL)).to(at::kInt);
+  return {hi, idx};
+}
+
+std::vector<at::Tensor> cache_topk_mxfp4(at::Tensor packed, at::Tensor scale,
+                                         at::Tensor inv_norm, at::Tensor q) {
+  return cache_topk_mxfp4_impl<false>("cache_topk_mxfp4", packed, scale, inv_norm, q,
+                                      nullptr, nullptr, nullptr, 0);
+}
+
+std::vector<at::Tensor> cache_topk_mxfp4_scoped(at::Tensor packed, at::Tensor scale,
+                                                at::Tensor inv_norm, at::Tensor q,
+                                                at::Tensor row_scope, at::Tensor row_expiry,
+                                                at::Tensor q_scope, int64_t now) {
+  return cache_topk_mxfp4_impl<true>("cache_topk_mxfp4_scoped", packed, scale, inv_norm, q,
+                                     &row_scope, &row_expiry, &q_scope, now);
+}
+
 at::Tensor kv_score_assign(at::Tensor stats, at::Tensor pred_tokens, double w_kv,
                            double w_q, double w_a) {
   check_cuda(stats, "stats");
@@ -856,6 +1000,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "cache_topk, row_scope must start 32-byte and row_expiry 16-byte "
         "aligned (the kernel reads 4 row tags as 16-byte vectors): pass "
         "tensors sliced from row 4k of their allocation, not e.g. row_scope[1:].");
+  m.def("mxfp4_quantize_rows", &mxfp4_quantize_rows,
+        "bf16 [n, dim] -> (packed e2m1 nibbles u8 [n, dim/2], E8M0 scale u8 "
+        "[n, dim/32], inv_norm f32 [n]); the format of aigw/ops/mxfp4_ref.py");
+  m.def("cache_topk_mxfp4", &cache_topk_mxfp4,
+        "cache_topk over an MXFP4 index (mxfp4_quantize_rows output) with "
+        "float8_e4m3fn queries: score = (row . q) * inv_norm[row]");
+  m.def("cache_topk_mxfp4_scoped", &cache_topk_mxfp4_scoped,
+        "cache_topk_mxfp4 under the row filter of cache_topk_scoped; idx -1 / "
+        "hi 0 for a query no row may answer");
   m.def("kv_score_assign", &kv_score_assign, "greedy KV-occupancy assignment");
   m.def("prefix_block_hashes", &prefix_block_hashes,
         "chained token-block hashes per request: (hashes int64[n_req, max_blocks], "

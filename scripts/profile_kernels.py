@@ -163,6 +163,31 @@ def main():
                 args.index_rows * (384 * elem_bytes + 12) / dt / 1e12, 3),
         }))
 
+    # MXFP4 index (fp4 rows x fp8 queries on the block-scaled MFMA): 208 B
+    # per dim-384 row (192 nibble bytes, 12 scale bytes, 4 inv_norm) next
+    # to the fp8 kernel on the same rows, at a serving batch and at --batch
+    unit = torch.nn.functional.normalize(index.float(), dim=1).to(torch.bfloat16)
+    packed, scale, inv_norm = tok.hip.mxfp4_quantize_rows(unit)
+    dt = timeit(lambda: tok.hip.mxfp4_quantize_rows(unit))
+    print(json.dumps({"kernel": "mxfp4_quantize_rows", "rows": args.index_rows,
+                      "ms": round(dt * 1e3, 3),
+                      "Mrows_per_s": round(args.index_rows / dt / 1e6, 1)}))
+    for n_q in sorted({1, 37, args.batch}):
+        qn = q8[:n_q].contiguous()
+        fp8_dt = timeit(lambda: tok.hip.cache_topk(index8, qn))
+        dt = timeit(lambda: tok.hip.cache_topk_mxfp4(packed, scale, inv_norm, qn))
+        sc_dt = timeit(lambda: tok.hip.cache_topk_mxfp4_scoped(
+            packed, scale, inv_norm, qn, row_scope, row_expiry, q_scope[:n_q], 1))
+        print(json.dumps({
+            "kernel": "cache_topk_mxfp4",
+            "rows": args.index_rows,
+            "queries": n_q,
+            "ms": round(dt * 1e3, 3),
+            "scoped_ms": round(sc_dt * 1e3, 3),
+            "fp8_ms": round(fp8_dt * 1e3, 3),
+            "TB_per_s_index_read": round(args.index_rows * 208 / dt / 1e12, 3),
+        }))
+
     stats = torch.rand(8, 4, device="cuda")
     stats[:, 1] = 1000
     pred = torch.rand(args.batch, device="cuda") * 100
