@@ -7,6 +7,7 @@
 #include <pybind11/stl.h>
 
 #include <cstdint>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -33,14 +34,22 @@ bool admission_count_lookup(GpuAdmissionDirect* a, const char* bytes, size_t n,
                             int32_t* counts_out, const int32_t* pending_slots,
                             int32_t* rows_out, float* scores_out);
 long long admission_cache_insert(GpuAdmissionDirect* a, int pending_slot);
+bool admission_submit(GpuAdmissionDirect* a, int set, const char* bytes,
+                      size_t n, const int64_t* offsets, int n_req,
+                      const int32_t* pending_slots);
+bool admission_wait(GpuAdmissionDirect* a, int set, int n_req,
+                    int32_t* counts_out, int32_t* rows_out, float* scores_out);
 
 }  // namespace aigw_fast
 
 namespace {
 
 // Direct test seam over the native admission path: the same C entry
-// points the server's batcher uses, one synchronous batch per call, no
-// HTTP and no threads. Adds no kernels and no behaviour of its own.
+// points the server's batcher uses, no HTTP and no threads: one
+// synchronous batch per call (count, count_lookup), or the batcher's own
+// submit/wait pair on either of the two batch sets. Adds no kernels and
+// no behaviour of its own; it only refuses arguments the C entry points
+// would take on trust (a pending slot outside the pool).
 class AdmissionProbe {
  public:
   AdmissionProbe(py::buffer htab_keys, py::buffer htab_rank, size_t max_bytes,
@@ -88,35 +97,85 @@ class AdmissionProbe {
   }
 
   std::vector<int32_t> count(const std::vector<std::string>& texts) {
-    pack(texts);
+    if (busy_[0]) throw std::runtime_error("set 0 has a batch in flight");
+    Packed& pk = packed_[0];
+    pack(texts, pk);
     std::vector<int32_t> counts(texts.size(), 0);
     bool ok;
     {
       py::gil_scoped_release release;
-      ok = admission_count(adm_, bytes_.data(), bytes_.size(), offs_.data(),
-                           (int)texts.size(), counts.data());
+      ok = admission_count(adm_, pk.bytes.data(), pk.bytes.size(),
+                           pk.offs.data(), (int)texts.size(), counts.data());
     }
     if (!ok) throw std::runtime_error("admission_count failed");
     return counts;
   }
 
-  py::tuple count_lookup(const std::vector<std::string>& texts) {
+  using Slots = std::optional<std::vector<int32_t>>;
+
+  py::tuple count_lookup(const std::vector<std::string>& texts,
+                         const Slots& slots_in) {
     if (!cache_on_) throw std::runtime_error("init_cache() first");
-    if ((long long)texts.size() > pending_cap_)
-      throw std::runtime_error("more texts than pending slots");
-    pack(texts);
+    if (busy_[0]) throw std::runtime_error("set 0 has a batch in flight");
+    std::vector<int32_t> slots = resolve_slots(texts.size(), slots_in);
+    Packed& pk = packed_[0];
+    pack(texts, pk);
     size_t nt = texts.size();
-    std::vector<int32_t> counts(nt, 0), rows(nt, -1), slots(nt);
+    std::vector<int32_t> counts(nt, 0), rows(nt, -1);
     std::vector<float> scores(nt, 0.f);
-    for (size_t i = 0; i < nt; ++i) slots[i] = (int32_t)i;
     bool ok;
     {
       py::gil_scoped_release release;
-      ok = admission_count_lookup(adm_, bytes_.data(), bytes_.size(),
-                                  offs_.data(), (int)nt, counts.data(),
+      ok = admission_count_lookup(adm_, pk.bytes.data(), pk.bytes.size(),
+                                  pk.offs.data(), (int)nt, counts.data(),
                                   slots.data(), rows.data(), scores.data());
     }
     if (!ok) throw std::runtime_error("admission_count_lookup failed");
+    return py::make_tuple(counts, rows, scores);
+  }
+
+  // The batcher's pair: launch a batch on set `set` and return at once;
+  // wait(set) collects it. slots == None: identity slots when the cache is
+  // on, a count-only batch otherwise.
+  void submit(int set, const std::vector<std::string>& texts,
+              const Slots& slots_in) {
+    check_set(set);
+    if (busy_[set]) throw std::runtime_error("set has a batch in flight");
+    if (slots_in && !cache_on_) throw std::runtime_error("init_cache() first");
+    std::vector<int32_t> slots;
+    if (cache_on_) slots = resolve_slots(texts.size(), slots_in);
+    Packed& pk = packed_[set];
+    pack(texts, pk);
+    bool ok;
+    {
+      py::gil_scoped_release release;
+      ok = admission_submit(adm_, set, pk.bytes.data(), pk.bytes.size(),
+                            pk.offs.data(), (int)texts.size(),
+                            cache_on_ ? slots.data() : nullptr);
+    }
+    if (!ok) throw std::runtime_error("admission_submit failed");
+    busy_[set] = true;
+    n_req_[set] = (int)texts.size();
+    with_cache_[set] = cache_on_;
+  }
+
+  py::tuple wait(int set) {
+    check_set(set);
+    if (!busy_[set]) throw std::runtime_error("nothing submitted on this set");
+    size_t nt = (size_t)n_req_[set];
+    bool cached = with_cache_[set];
+    std::vector<int32_t> counts(nt, 0), rows(nt, -1);
+    std::vector<float> scores(nt, 0.f);
+    bool ok;
+    {
+      py::gil_scoped_release release;
+      ok = admission_wait(adm_, set, (int)nt, counts.data(),
+                          cached ? rows.data() : nullptr,
+                          cached ? scores.data() : nullptr);
+    }
+    busy_[set] = false;
+    if (!ok) throw std::runtime_error("admission_wait failed");
+    if (!cached) return py::make_tuple(counts, py::none(), py::none());
     return py::make_tuple(counts, rows, scores);
   }
 
@@ -128,17 +187,54 @@ class AdmissionProbe {
   }
 
  private:
-  void pack(const std::vector<std::string>& texts) {
+  struct Packed {
+    std::string bytes;
+    std::vector<int64_t> offs;
+  };
+
+  void pack(const std::vector<std::string>& texts, Packed& pk) const {
     if (texts.empty() || (long long)texts.size() > max_req_)
       throw std::runtime_error("text count out of range");
-    bytes_.clear();
-    offs_.clear();
-    for (const auto& t : texts) {
-      offs_.push_back((int64_t)bytes_.size());
-      bytes_.append(t);
-    }
-    if (bytes_.empty() || bytes_.size() > max_bytes_)
+    size_t total = 0;
+    for (const auto& t : texts) total += t.size();
+    if (total == 0 || total > max_bytes_)
       throw std::runtime_error("batch bytes out of range");
+    pk.bytes.clear();
+    pk.offs.clear();
+    for (const auto& t : texts) {
+      pk.offs.push_back((int64_t)pk.bytes.size());
+      pk.bytes.append(t);
+    }
+  }
+
+  static void check_set(int set) {
+    if (set != 0 && set != 1) throw std::runtime_error("set must be 0 or 1");
+  }
+
+  // One pending slot per text: -1 (park nothing) or a distinct slot inside
+  // the pool. park_pending_kernel writes wherever the slot points, so
+  // anything else is refused here, before any GPU call.
+  std::vector<int32_t> resolve_slots(size_t nt, const Slots& slots_in) const {
+    std::vector<int32_t> slots;
+    if (!slots_in) {
+      if ((long long)nt > pending_cap_)
+        throw std::runtime_error("more texts than pending slots");
+      slots.resize(nt);
+      for (size_t i = 0; i < nt; ++i) slots[i] = (int32_t)i;
+      return slots;
+    }
+    slots = *slots_in;
+    if (slots.size() != nt)
+      throw std::runtime_error("slots must hold one entry per text");
+    std::vector<char> seen((size_t)pending_cap_, 0);
+    for (int32_t sl : slots) {
+      if (sl == -1) continue;
+      if (sl < 0 || sl >= pending_cap_)
+        throw std::runtime_error("pending slot out of range");
+      if (seen[(size_t)sl]) throw std::runtime_error("duplicate pending slot");
+      seen[(size_t)sl] = 1;
+    }
+    return slots;
   }
 
   GpuAdmissionDirect* adm_ = nullptr;
@@ -146,8 +242,10 @@ class AdmissionProbe {
   int max_req_;
   int pending_cap_ = 0;
   bool cache_on_ = false;
-  std::string bytes_;
-  std::vector<int64_t> offs_;
+  Packed packed_[2];
+  bool busy_[2] = {false, false};
+  bool with_cache_[2] = {false, false};
+  int n_req_[2] = {0, 0};
 };
 
 }  // namespace
@@ -163,7 +261,11 @@ PYBIND11_MODULE(aigw_fast, m) {
            py::arg("proj_u16"), py::arg("capacity"), py::arg("threshold"),
            py::arg("pending_cap"), py::arg("fp8"))
       .def("count", &AdmissionProbe::count, py::arg("texts"))
-      .def("count_lookup", &AdmissionProbe::count_lookup, py::arg("texts"))
+      .def("count_lookup", &AdmissionProbe::count_lookup, py::arg("texts"),
+           py::arg("slots") = py::none())
+      .def("submit", &AdmissionProbe::submit, py::arg("set"), py::arg("texts"),
+           py::arg("slots") = py::none())
+      .def("wait", &AdmissionProbe::wait, py::arg("set"))
       .def("insert", &AdmissionProbe::insert, py::arg("slot"));
 
   py::class_<FastMock>(m, "FastMock")

@@ -4,6 +4,9 @@ Plain helper module (no tests here): tests/test_kernel_checks_cpu.py and
 tests/test_kernel_checks_scoped_cpu.py prove on the CPU that each comparator
 rejects deliberately wrong emulations, and tests/test_gpu_kernel_edges.py
 and tests/test_gpu_cache_scoped_edges.py feed them the real kernels' outputs.
+The native cache tail's comparator, ring model and emulation at the end are
+proven by tests/test_kernel_checks_probe_cpu.py and fed by
+tests/test_gpu_admission_cache_edges.py (cases in tests/probe_tail_cases.py).
 
 Every bound below is an a-priori floating-point error bound for the
 operation, never a figure taken from the kernel under test.
@@ -774,3 +777,384 @@ def probe_score_stats(ids_list, emb, proj, fp8: bool) -> dict:
     off.fill_diagonal_(-float("inf"))
     lead = float((self64 - off.max(dim=1).values).min())
     return {"q": q64, "self": self64, "measured": measured, "min_lead": lead}
+
+
+# ---------------------------------------------------------------------------
+# native cache tail edges (tests/test_gpu_admission_cache_edges.py, proven on
+# the CPU by tests/test_kernel_checks_probe_cpu.py)
+# ---------------------------------------------------------------------------
+
+def probe_variant_texts(texts: list[bytes]) -> list[bytes]:
+    """For each lookup text a second text that shares most of its words:
+    the text, a space and the first 12 bytes of the next text. Its best
+    row is its own original, at a cross score well under a self-match."""
+    n = len(texts)
+    return [texts[i] + b" " + texts[(i + 1) % n][:12] for i in range(n)]
+
+
+PROBE_EDGE_COUNTS = (1, 31, 32, 33, 4095, 4096, 4097, 4097 + 130)
+_MERGE_LETTERS = b"etaoinshrdlucmfwypvbgkjqxz"
+
+
+def _draw(alphabet: bytes, n: int, seed: int) -> bytes:
+    rng = np.random.default_rng(seed)
+    return bytes(alphabet[int(i)] for i in rng.integers(0, len(alphabet), n))
+
+
+def _cut_to_count(ref, text: bytes, target: int) -> bytes:
+    """The prefix of `text` at which the oracle reaches `target` tokens."""
+    from aigw.ops.bpe_ref import segment_starts
+
+    starts = segment_starts(text, [0]) + [len(text)]
+    total = 0
+    for s, e in zip(starts, starts[1:]):
+        c = len(ref.encode_segment(text[s:e]))
+        if total + c == target:
+            return text[:e]
+        if total + c > target:
+            for cut in range(s + 1, e):
+                if total + len(ref.encode_segment(text[s:cut])) == target:
+                    return text[:cut]
+            raise AssertionError("no cut reaches the target count")
+        total += c
+    raise AssertionError("text too short for the target count")
+
+
+def probe_count_edge_texts(ref, long: bool = True) -> dict:
+    """One text per oracle token count in PROBE_EDGE_COUNTS (around P = 32
+    blocks per request, and around 4096 = P * STAGE where a block's chunk
+    needs a second staging round) and a variant of each. Text k is prose
+    over its own alphabet (three merging letters, four bytes >= 0x80 and a
+    digit that never merge, space), so that no two edge texts embed close
+    together; a long text's variant replaces its last ~5 % of tokens with
+    bytes of another alphabet, a short text's appends three such bytes.
+    long=False leaves the texts above 33 tokens out (CPU proof only)."""
+    counts = [c for c in PROBE_EDGE_COUNTS if long or c <= 33]
+    texts, variants = [], []
+    for k, c in enumerate(counts):
+        alphabet = (_MERGE_LETTERS[3 * k:3 * k + 3] + b" %d" % k
+                    + bytes(range(0x80 + 6 * k, 0x80 + 6 * k + 4)))
+        tail = bytes(range(0xC0 + 4 * k, 0xC0 + 4 * k + 4))
+        prose = _draw(alphabet, 3 * c + 64, 4000 + k)
+        text = _cut_to_count(ref, prose, c)
+        if c > 33:
+            keep = c - c // 20
+            variant = _cut_to_count(ref, prose, keep) + _draw(tail, c - keep, 4100 + k)
+        else:
+            variant = text + b" " + _draw(tail, 2, 4100 + k)
+        texts.append(text)
+        variants.append(variant)
+    return {"counts": counts, "texts": texts, "variants": variants}
+
+
+def probe_pool_fp32(ids, emb32: np.ndarray, mutant=None, prev_ids=None):
+    """Mean of the token rows in fp32, summed one by one in order as the
+    kernel's blocks do (not torch's pairwise mean). The pooling mutants of
+    emulate_probe_tail live here."""
+    if mutant == "pool_prev_request" and prev_ids is not None:
+        ids = prev_ids
+    ids = list(ids)
+    if mutant == "drop_last_token":
+        ids = ids[:-1]
+    if mutant == "chunk_first_128":
+        chunk = (len(ids) + 31) // 32
+        ids = [t for j, t in enumerate(ids) if chunk == 0 or j % chunk < 128]
+    acc = np.zeros(emb32.shape[1], dtype=np.float32)
+    for t in ids:
+        acc += emb32[t]
+    if ids:
+        acc /= np.float32(len(ids) + (mutant == "mean_div_c_plus_1"))
+    return acc
+
+
+def probe_plain_fp32_sequential(ids_list, emb, proj, fp8: bool, mutant=None):
+    """probe_plain_fp32 with the sequential fp32 mean: the yardstick for
+    texts of thousands of tokens, and the embed half of the emulation."""
+    emb32 = emb.float().numpy()
+    pooled = torch.from_numpy(np.stack([
+        probe_pool_fp32(ids, emb32, mutant, ids_list[r - 1] if r else None)
+        for r, ids in enumerate(ids_list)])).to(torch.bfloat16)
+    g = pooled.float() @ proj.float().T
+    qv = (g * torch.rsqrt((g * g).sum(dim=1, keepdim=True) + 1e-12)).to(torch.bfloat16)
+    if fp8:
+        qv = qv.to(torch.float8_e4m3fn)
+    return qv.float()
+
+
+# Largest |score (plain fp32, sequential mean) - score (fp64 mirrored
+# reference)| over EVERY cell of the score matrix of the 130 lookup texts,
+# their 130 variants and the one foreign text (68 121 cells: the one-row and
+# partial-index tests check cells far from any text's best), measured on the
+# CPU per index format. bf16: 13 of 100 224 roundings land on the other side
+# of a boundary, worst cell 2.778e-5 (cross scores alone 1.21e-5, self
+# scores 2.51e-5). fp8: a single e4m3 flip (one step is 2^-4 relative) moves
+# one cell by 2.441e-4 (cross scores alone 2.29e-5, self scores 8.0e-5). The
+# 16 count-edge texts and variants, 4227 tokens the longest, measure 0.0 in
+# both formats (no flip at all), so the long texts need no constant of their
+# own. The allowance is 4x the measurement, as for PROBE_SCORE_ALLOWANCE.
+PROBE_EDGE_MEASURED_FP32_DISAGREEMENT = {False: 2.78e-5, True: 2.45e-4}  # bf16, fp8
+PROBE_EDGE_ALLOWANCE = {f: 4 * v for f, v in
+                        PROBE_EDGE_MEASURED_FP32_DISAGREEMENT.items()}
+
+
+def probe_ring_reference(inserted, capacity: int, q, threshold: float) -> dict:
+    """CPU model of what the native cache must return. `inserted` is the
+    (n, dim) fp64 matrix of the vectors passed to insert(), in call order
+    (fp64 mirrored reference vectors); insert k writes row k % capacity
+    (head = (head + 1) % cap) and the visible row count is
+    min(max(row + 1, visible), cap). Per query of `q` (fp64): the argmax
+    row over the visible rows and its score, or -1 / 0.0 under the
+    threshold; the lead over the best row that does not tie exactly; the
+    set of rows that tie exactly with the winner (duplicates); the
+    distance of the best score from the threshold."""
+    n_ins = int(inserted.shape[0]) if len(inserted) else 0
+    n_q = int(q.shape[0])
+    ring = {}
+    head = visible = 0
+    insert_rows = []
+    for k in range(n_ins):
+        row, head = head, (head + 1) % capacity
+        ring[row] = k
+        visible = min(max(row + 1, visible), capacity)
+        insert_rows.append(row)
+    out = {"insert_rows": insert_rows, "visible": visible, "threshold": threshold}
+    if visible == 0:
+        out.update(rows=[-1] * n_q, scores=[0.0] * n_q, best=[None] * n_q,
+                   gaps=[float("inf")] * n_q, ties=[set() for _ in range(n_q)],
+                   margins=[float("inf")] * n_q)
+        return out
+    assert sorted(ring) == list(range(visible))
+    index = torch.stack([inserted[ring[r]] for r in range(visible)]).to(torch.float64)
+    s = q.to(torch.float64) @ index.T  # (n_q, visible)
+    best = s.max(dim=1).values
+    rows, scores, gaps, ties, margins = [], [], [], [], []
+    for b in range(n_q):
+        tie = s[b] == best[b]
+        rest = s[b][~tie]
+        gaps.append(float(best[b] - rest.max()) if rest.numel() else float("inf"))
+        ties.append(set(torch.nonzero(tie).flatten().tolist()))
+        margins.append(abs(float(best[b]) - threshold))
+        hit = float(best[b]) >= threshold
+        rows.append(int(torch.argmax(s[b])) if hit else -1)
+        scores.append(float(best[b]) if hit else 0.0)
+    out.update(rows=rows, scores=scores, best=best.tolist(), gaps=gaps,
+               ties=ties, margins=margins)
+    return out
+
+
+def probe_fit_queries(ref_result: dict, allowance: float) -> list[int]:
+    """The queries check_probe_lookup would not refuse (reference only)."""
+    return [b for b, (g, m) in enumerate(zip(ref_result["gaps"], ref_result["margins"]))
+            if g >= 10 * allowance and m >= 10 * allowance]
+
+
+def check_probe_lookup(rows, scores, ref_result: dict, allowance: float) -> dict:
+    """Native lookup result against probe_ring_reference: the row must be
+    the reference argmax or one of its exact duplicates (the documented tie
+    rule), the score within `allowance` of the reference score, and a query
+    under the threshold must return exactly -1 and 0.0. Inputs whose
+    reference lead over the runner-up, or whose best score's distance from
+    the threshold, is under 10x the allowance are refused: an exact-row or
+    hit/miss assertion on them would be a coin toss."""
+    rows, scores = _as_list(rows), _as_list(scores)
+    n_q = len(ref_result["rows"])
+    assert len(rows) == n_q and len(scores) == n_q, "result length"
+    max_err = 0.0
+    for b in range(n_q):
+        gap, margin = ref_result["gaps"][b], ref_result["margins"][b]
+        assert gap >= 10 * allowance, (
+            f"unfit: query {b} leads its runner-up by {gap:.3e} < 10 x allowance")
+        assert margin >= 10 * allowance, (
+            f"unfit: query {b} best score is {margin:.3e} from the threshold")
+        want_row, want = ref_result["rows"][b], ref_result["scores"][b]
+        got_row, got = int(rows[b]), float(scores[b])
+        if want_row < 0:
+            assert got_row == -1 and got == 0.0, (
+                f"under threshold: query {b} must return -1 / 0.0, got "
+                f"{got_row} / {got!r} (reference best {ref_result['best'][b]})")
+            continue
+        assert got_row != -1, (
+            f"lost hit: query {b} returned -1 / {got!r}, reference row "
+            f"{want_row} score {want:.6f} over threshold {ref_result['threshold']}")
+        assert got_row in ref_result["ties"][b], (
+            f"wrong row: query {b} returned row {got_row} ({got!r}), reference "
+            f"rows {sorted(ref_result['ties'][b])[:8]} score {want:.6f}")
+        err = abs(got - want)
+        assert err <= allowance, (  # also false for a NaN score
+            f"score off: query {b} row {got_row} score {got!r}, reference "
+            f"{want:.7f}, |err| {err:.3e} > allowance {allowance:.3e}")
+        max_err = max(max_err, err)
+    return {"max_err": max_err,
+            "min_gap": min(ref_result["gaps"], default=float("inf")),
+            "min_margin": min(ref_result["margins"], default=float("inf"))}
+
+
+PROBE_TAIL_MUTANTS = (
+    "drop_last_token",         # the last token of a request not pooled
+    "chunk_first_128",         # tokens past the first 128 of a block's chunk dropped
+    "mean_div_c_plus_1",       # the mean divided by c + 1
+    "pool_prev_request",       # request r pooled from request r - 1's token range
+    "negative_wrong_branch",   # a negative best score decoded as a positive one
+    "threshold_gt_zero",       # the cut applied as score > 0
+    "rows_past_1024_unscanned",  # only the first CTA's rows scanned
+    "ring_wrap_head_plus_1",   # once wrapped, the ring writes at head + 1
+    "visible_reset_on_wrap",   # visible rows set to row + 1 without the max
+    "neg_slot_to_slot0",       # a -1 slot parked in slot 0
+    "identity_slots",          # request r parked in slot r whatever was passed
+    "set1_returns_set0",       # wait(1) hands out set 0's results
+)
+
+
+def _decode_best(score: float, wrong_branch: bool) -> float:
+    """wait_set's decode of the packed orderable float."""
+    hi = order_float(score)
+    bits = (hi ^ 0x80000000) if (hi >= 0x80000000 or wrong_branch) else (~hi & 0xFFFFFFFF)
+    return struct.unpack("<f", struct.pack("<I", bits))[0]
+
+
+def emulate_probe_tail(ids_list, emb, proj, fp8: bool, index, visible: int,
+                       threshold: float, mutant=None, q=None):
+    """Plain fp32 CPU emulation of the native cache tail for one batch:
+    oracle ids -> sequential fp32 mean -> bf16 -> projection -> normalise
+    -> bf16 (-> e4m3) -> best of the `visible` first rows of `index`
+    (fp32, holding index-format values) -> packed score decode ->
+    threshold. Returns (q, rows, scores); q is what the batch parks.
+    `mutant` (PROBE_TAIL_MUTANTS) exists only so the CPU self-test can
+    build deliberately wrong variants; a precomputed `q` skips the embed."""
+    assert mutant is None or mutant in PROBE_TAIL_MUTANTS
+    if q is None:
+        q = probe_plain_fp32_sequential(ids_list, emb, proj, fp8, mutant)
+    n_q = q.shape[0]
+    rows, scores = [-1] * n_q, [0.0] * n_q
+    if mutant == "rows_past_1024_unscanned":
+        visible = min(visible, 1024)
+    if visible > 0:
+        s = q @ index[:visible].T
+        best = s.max(dim=1).values
+        for b in range(n_q):
+            # ties go to the highest row, as the packed atomicMax's do
+            row = int(torch.nonzero(s[b] == best[b]).flatten()[-1])
+            score = _decode_best(float(best[b]), mutant == "negative_wrong_branch")
+            hit = score > 0 if mutant == "threshold_gt_zero" else score >= threshold
+            if hit:
+                rows[b], scores[b] = row, score
+    return q, rows, scores
+
+
+class EmulatedProbe:
+    """aigw_fast.AdmissionProbe's interface over emulate_probe_tail and a
+    plain ring/pending-pool model, so that the GPU test cases
+    (tests/probe_tail_cases.py) can be run against deliberately wrong
+    variants on the CPU. `ids_of` maps a text to its oracle ids."""
+
+    def __init__(self, ids_of, emb, proj, max_req: int, mutant=None, q_cache=None):
+        self.ids_of, self.emb, self.proj = ids_of, emb, proj
+        self.max_req, self.mutant = max_req, mutant
+        self.cache_on = False
+        self.sets = [None, None]
+        self.last = [None, None]
+        # embeds are shared between probes unless the mutant changes them
+        pooling = mutant in PROBE_TAIL_MUTANTS[:4]
+        self.q_cache = None if pooling or q_cache is None else q_cache
+
+    def init_cache(self, emb_u16, proj_u16, capacity, threshold, pending_cap, fp8):
+        assert not self.cache_on  # the weights came with the constructor
+        self.cap, self.threshold, self.fp8 = capacity, threshold, fp8
+        self.pending_cap = pending_cap
+        self.index = torch.zeros(capacity, PROBE_DIM)
+        self.pending = torch.zeros(pending_cap, PROBE_DIM)
+        self.head = self.visible = 0
+        self.wrapped = False
+        self.cache_on = True
+
+    def _slots(self, n, slots):
+        if slots is None:
+            if n > self.pending_cap:
+                raise RuntimeError("more texts than pending slots")
+            return list(range(n))
+        slots = [int(s) for s in slots]
+        used = [s for s in slots if s != -1]
+        if (len(slots) != n or any(not 0 <= s < self.pending_cap for s in used)
+                or len(set(used)) != len(used)):
+            raise RuntimeError("bad pending slots")
+        return slots
+
+    def _embed(self, texts):
+        ids = [self.ids_of(t) for t in texts]
+        if self.q_cache is None:
+            return ids, probe_plain_fp32_sequential(ids, self.emb, self.proj,
+                                                    self.fp8, self.mutant)
+        key = self.fp8
+        missing = [t for t in dict.fromkeys(texts) if (key, t) not in self.q_cache]
+        if missing:
+            qm = probe_plain_fp32_sequential([self.ids_of(t) for t in missing],
+                                             self.emb, self.proj, self.fp8)
+            self.q_cache.update({(key, t): qm[i] for i, t in enumerate(missing)})
+        return ids, torch.stack([self.q_cache[(key, t)] for t in texts])
+
+    def _run(self, texts, slots):
+        if not texts or len(texts) > self.max_req or not any(texts):
+            raise RuntimeError("batch out of range")
+        if slots is None:
+            return [len(self.ids_of(t)) for t in texts], None, None
+        ids, q = self._embed(texts)
+        q, rows, scores = emulate_probe_tail(
+            ids, self.emb, self.proj, self.fp8, self.index, self.visible,
+            self.threshold, self.mutant, q=q)
+        for r, slot in enumerate(slots):
+            if self.mutant == "identity_slots":
+                slot = r
+            elif slot < 0 and self.mutant == "neg_slot_to_slot0":
+                slot = 0
+            if slot >= 0:
+                self.pending[slot] = q[r]
+        return [len(i) for i in ids], rows, scores
+
+    def count(self, texts):
+        return self._run(texts, None)[0]
+
+    def count_lookup(self, texts, slots=None):
+        if not self.cache_on:
+            raise RuntimeError("init_cache() first")
+        self.submit(0, texts, slots)
+        return self.wait(0)
+
+    def submit(self, s, texts, slots=None):
+        if s not in (0, 1):
+            raise RuntimeError("set must be 0 or 1")
+        if self.sets[s] is not None:
+            raise RuntimeError("set has a batch in flight")
+        if slots is not None and not self.cache_on:
+            raise RuntimeError("init_cache() first")
+        slots = self._slots(len(texts), slots) if self.cache_on else None
+        self.sets[s] = self._run(list(texts), slots)
+
+    def wait(self, s):
+        if s not in (0, 1):
+            raise RuntimeError("set must be 0 or 1")
+        if self.sets[s] is None:
+            raise RuntimeError("nothing submitted on this set")
+        own, self.sets[s] = self.sets[s], None
+        self.last[s] = own
+        if s == 1 and self.mutant == "set1_returns_set0":
+            n = len(own[0])
+            other = self.last[0] or ([], [], [])
+            pad = lambda x, fill: None if own[1] is None else (list(x or []) + [fill] * n)[:n]
+            return ((list(other[0]) + [0] * n)[:n], pad(other[1], -1), pad(other[2], 0.0))
+        return own
+
+    def insert(self, slot):
+        if not self.cache_on or not 0 <= slot < self.pending_cap:
+            raise RuntimeError("cache insert failed")
+        row = self.head
+        self.head = (self.head + 1) % self.cap
+        self.wrapped = self.wrapped or self.head == 0
+        at = row
+        if self.mutant == "ring_wrap_head_plus_1" and self.wrapped and self.head != 0:
+            at = (row + 1) % self.cap
+        self.index[at] = self.pending[slot]
+        if self.mutant == "visible_reset_on_wrap":
+            self.visible = row + 1  # differs only once row + 1 < visible
+        else:
+            self.visible = min(max(row + 1, self.visible), self.cap)
+        return row
