@@ -90,6 +90,7 @@ async def _run_shard(args, rank: int = 0, world: int = 1) -> None:
                 cache_index_dtype=getattr(args, "cache_index_dtype", "bf16"),
                 cache_scoped=getattr(args, "cache_scope", "value") == "index",
                 cache_ttl_s=getattr(args, "cache_ttl_s", 0) or None,
+                cache_candidates=getattr(args, "cache_candidates", 1),
             )
             if gpu_socket:
                 from aigw.gpu.service import GPUServiceHost
@@ -264,6 +265,28 @@ def _check_cache_flags(args) -> None:
         from aigw.extproc.fast_front import MXFP4_NATIVE_FRONT
 
         raise SystemExit(MXFP4_NATIVE_FRONT)
+    candidates = getattr(args, "cache_candidates", 1)
+    if not 1 <= candidates <= 8:
+        raise SystemExit("--semantic-cache-candidates must be 1..8")
+    if candidates > 1 and args.gpu and args.semantic_cache:
+        if args.front == "fast":
+            # the native front's in-process lookup is the arg-max kernel
+            raise SystemExit(
+                "--semantic-cache-candidates above 1 is not supported by the "
+                "native front (--front fast) yet: its in-process cache looks up "
+                "one row per request — use --front lean")
+        if getattr(args, "cache_index_dtype", "bf16") == "mxfp4":
+            raise SystemExit(
+                "--semantic-cache-candidates above 1 is not supported with "
+                "--cache-index-dtype mxfp4 yet: the k-best lookup kernel reads "
+                "bf16 and fp8 indexes only — use bf16 or fp8")
+        if getattr(args, "workers", 1) > 1:
+            # workers reach the GPU over the shard's socket, which carries
+            # one cached value per lookup
+            raise SystemExit(
+                "--semantic-cache-candidates above 1 is not supported with "
+                "--workers above 1 yet: the workers' GPU socket returns one "
+                "candidate per lookup — use --workers 1")
 
 
 def cmd_run(args) -> int:
@@ -403,6 +426,15 @@ def main(argv=None) -> int:
     runp.add_argument("--semantic-cache-ttl", type=float, default=0.0,
                       dest="cache_ttl_s", metavar="SECONDS",
                       help="expire cached rows after SECONDS (0 = never)")
+    runp.add_argument("--semantic-cache-candidates", type=int, default=1,
+                      dest="cache_candidates", metavar="N",
+                      help="index rows fetched per lookup (1..8): above 1 a request "
+                           "takes the best row whose value carries its own tag "
+                           "(stream flag, model, route, params) instead of missing "
+                           "when the single best row is another caller's; --workers 1, "
+                           "bf16/fp8 index, not --front fast. The lookup gets slower "
+                           "with N: at 8 on a bf16 index it currently costs more than "
+                           "an unfused GEMM + top-k (profiles/cache_topk_k.md)")
     runp.set_defaults(fn=cmd_run)
 
     tr = sub.add_parser("translate", help="CRD bundle -> filter config YAML")

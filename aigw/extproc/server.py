@@ -696,9 +696,17 @@ class GatewayServer:
             # rows by the tag, so two scopes storing the same prompt each
             # find their own row; the value-tag compare below stays either
             # way (a scope-id collision then costs a miss, never a leak).
-            hit, cache_key_vec = await self.gpu.cache_lookup_text(
-                chat_text or b" ", **self._cache_scope_kw(cache_tag)
-            )
+            if getattr(self.gpu, "cache_candidates", 1) > 1:
+                # k-best lookup: the best row may be another tag's copy of
+                # the same prompt; take the best one that is this request's
+                cands, cache_key_vec = await self.gpu.cache_lookup_text_k(
+                    chat_text or b" ", **self._cache_scope_kw(cache_tag)
+                )
+                hit = next((v for v in cands if v[: len(cache_tag)] == cache_tag), None)
+            else:
+                hit, cache_key_vec = await self.gpu.cache_lookup_text(
+                    chat_text or b" ", **self._cache_scope_kw(cache_tag)
+                )
             if hit is not None and hit[: len(cache_tag)] == cache_tag:
                 self.metrics._child(self.metrics.cache_events, ("hit",)).inc()
                 body_bytes = hit[len(cache_tag):]

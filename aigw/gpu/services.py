@@ -87,12 +87,20 @@ class GPUServices:
         # | "mxfp4" (3.7x rows/GB at dim 384)
         cache_scoped: bool = False,  # filter cache rows by scope in the index
         cache_ttl_s: Optional[float] = None,  # None: cached rows never expire
+        # index rows fetched per lookup (1..8); above 1 a caller can walk
+        # past a best row whose value is not the one it wants
+        cache_candidates: int = 1,
         window_ms: float = 0.1,
         max_batch: int = 128,
     ):
         from aigw.ops.semcache import SemanticCache
         from aigw.ops.tokenizer import GPUTokenizer
 
+        if not 1 <= cache_candidates <= 8:
+            raise ValueError(f"cache_candidates must be 1..8, got {cache_candidates}")
+        if cache_candidates > 1 and cache_index_dtype == "mxfp4":
+            raise ValueError("cache_candidates > 1 needs a bf16 or fp8 cache index")
+        self.cache_candidates = cache_candidates
         self.device = device
         self.tokenizer = GPUTokenizer(n_merges=n_merges, device=device)
         self.cache: Optional[SemanticCache] = (
@@ -214,7 +222,9 @@ class GPUServices:
         over every text of every queued batch; for vector-wanting items,
         ONE batched embedding GEMM and ONE fused index lookup (a lookup per
         request would mean a single-query kernel launch each). Returns one
-        result list per item of (count, vec, cached_value_or_None)."""
+        result list per item of (count, vec, cached_value_or_None); with
+        cache_candidates > 1 the third element is the list of the
+        candidates' stored values, best first."""
         texts = []
         spans = []
         for it in batch:
@@ -234,8 +244,14 @@ class GPUServices:
                     scopes.extend(it.scopes if it.scopes is not None
                                   else [0] * len(it.texts))
             # one fused kernel, all queries
-            found = self.cache.lookup(qvecs, scopes=scopes)
-            hits = [self.cache.get(h[0]) if h is not None else None for h in found]
+            if self.cache_candidates > 1:
+                found = self.cache.lookup_k(qvecs, self.cache_candidates, scopes=scopes)
+                # a slot whose value is gone is skipped, not a miss
+                hits = [[v for v in (self.cache.get(slot) for slot, _ in cands)
+                         if v is not None] for cands in found]
+            else:
+                found = self.cache.lookup(qvecs, scopes=scopes)
+                hits = [self.cache.get(h[0]) if h is not None else None for h in found]
         results = []
         for it, (lo, hi) in zip(batch, spans):
             if it.want_vec and qvecs is not None:
@@ -247,6 +263,12 @@ class GPUServices:
         return results
 
     # ---- public API ----------------------------------------------------------
+
+    def _first(self, hit):
+        """The single-value view of a lookup result: the best candidate."""
+        if self.cache_candidates > 1:
+            return hit[0] if hit else None
+        return hit
 
     async def count_request_tokens(self, body: dict) -> int:
         count, _, _ = await self._submit(extract_chat_text(body), want_vec=False)
@@ -268,7 +290,16 @@ class GPUServices:
         flush — no per-request kernel launches. ``scope`` (a tag's bytes or
         an id) restricts the lookup to that scope's rows."""
         _, vec, hit = await self._submit(text or b" ", want_vec=True, scope=scope)
-        return hit, vec
+        return self._first(hit), vec
+
+    async def cache_lookup_text_k(self, text: bytes, scope=None):
+        """cache_lookup_text returning every candidate: (stored values of
+        the up to cache_candidates best rows over the threshold, best first,
+        and the query vector)."""
+        _, vec, hit = await self._submit(text or b" ", want_vec=True, scope=scope)
+        if self.cache_candidates > 1:
+            return list(hit or ()), vec
+        return ([] if hit is None else [hit]), vec
 
     async def lookup_texts_batch(self, texts: list[bytes], scopes=None):
         """Batch entry for the shard GPU service: one future per worker
@@ -281,7 +312,7 @@ class GPUServices:
         results = await self._submit_batch(
             [t or b" " for t in texts], want_vec=True, scopes=scopes
         )
-        return [(hit, vec) for _c, vec, hit in results]
+        return [(self._first(hit), vec) for _c, vec, hit in results]
 
     async def tokenize(self, text) -> list[int]:
         if isinstance(text, str):
@@ -299,7 +330,7 @@ class GPUServices:
         _, vec, hit = await self._submit(
             extract_chat_text(body), want_vec=True, scope=scope
         )
-        return hit, vec
+        return self._first(hit), vec
 
     async def cache_insert(self, vec, response: bytes, scope=None, ttl_s=None) -> None:
         if vec is None or self.cache is None:

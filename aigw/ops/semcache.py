@@ -191,6 +191,50 @@ class SemanticCache:
             out.append((i, score) if score >= self.threshold else None)
         return out
 
+    def lookup_k(
+        self, queries: torch.Tensor, k: int, scopes: Optional[list[int]] = None
+    ) -> list[list[tuple[int, float]]]:
+        """Per query: the at most k best index rows as (slot, score), best
+        first (the higher slot first among equal scores), keeping only
+        scores at or over the threshold. Rows are filtered exactly when
+        ``lookup`` would filter them. One fused pass over the index
+        (cache_topk_k); bf16 and fp8 indexes only.
+
+        The first pair is not always what ``lookup`` returns: while no tag is
+        in play ``lookup`` runs the unfiltered arg-max kernel, which gives an
+        exact score tie between two rows of one aligned group of four slots
+        (the same vector inserted back to back at slots 4m and 4m + 1) to the
+        lower slot; ``lookup_k`` lists the higher slot first everywhere."""
+        if self.mxfp4:
+            raise ValueError(
+                "lookup_k: k-best lookup is not implemented for index_dtype='mxfp4' "
+                "(bf16 and fp8 only)")
+        n = queries.shape[0]
+        if self.size == 0:
+            return [[] for _ in range(n)]
+        view = self.index[: self.size]
+        tags = ()
+        if self._filtering or scopes is not None:
+            q_scope = torch.tensor(
+                list(scopes) if scopes is not None else [0] * n,
+                dtype=torch.int64, device=self.device,
+            )
+            if q_scope.shape[0] != n:
+                raise ValueError("scopes must hold one id per query")
+            tags = (self.row_scope[: self.size], self.row_expiry[: self.size])
+            now = self.now()
+        out: list[list[tuple[int, float]]] = []
+        for q0 in range(0, n, 256):  # kernel cap: 256 q/call
+            qs = queries[q0 : q0 + 256].to(self.query_dtype).contiguous()
+            if tags:
+                h, i = self.hip.cache_topk_k(view, qs, k, *tags, q_scope[q0 : q0 + 256], now)
+            else:
+                h, i = self.hip.cache_topk_k(view, qs, k)
+            for hs, rows in zip(h.cpu().tolist(), i.cpu().tolist()):
+                found = [(r, _unorder(x)) for x, r in zip(hs, rows) if r >= 0]
+                out.append([(r, s) for r, s in found if s >= self.threshold])
+        return out
+
     def get(self, slot: int) -> Optional[bytes]:
         return self.values.get(slot)
 

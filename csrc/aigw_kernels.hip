@@ -53,6 +53,12 @@ static inline hipStream_t current_stream() {
 #include "cache_kernels.cuh"
 
 // ---------------------------------------------------------------------------
+// 3b'. k-best (k <= 8) cache lookup: per-wave LDS lists + a merge launch
+// ---------------------------------------------------------------------------
+
+#include "cache_kbest_kernels.cuh"
+
+// ---------------------------------------------------------------------------
 // 3c. MXFP4 cache index: row quantiser + block-scaled fp4 x fp8 MFMA lookup
 // ---------------------------------------------------------------------------
 
@@ -501,6 +507,135 @@ std::vector<at::Tensor> cache_topk_scoped(at::Tensor index, at::Tensor q,
   else
     launch_cache_topk_scoped<CacheElemBf16>(index, q, row_scope, row_expiry, q_scope,
                                             (int)now, best);
+  auto hi = best.bitwise_right_shift(32).to(at::kLong);
+  auto idx = at::where(best == 0, -1, best.bitwise_and(0xFFFFFFFFLL)).to(at::kInt);
+  return {hi, idx};
+}
+
+// The k best eligible rows per query (cache_kbest_kernels.cuh): one scan
+// launch per query pass writes every block's sorted k-best to `part`
+// ([blocks, n_q, k] keys), one merge launch folds them into `best`
+// ([n_q, k] keys, descending, 0 = no row).
+template <class E, bool SCOPED>
+static void launch_cache_topk_k(const at::Tensor& index, const at::Tensor& q, int k,
+                                const long long* rs, const int* re, const long long* qsc,
+                                int now, at::Tensor& best) {
+  using elem = typename E::elem;
+  constexpr int ROWTILES = 16;
+  long long n_rows = index.size(0);
+  int n_q = (int)q.size(0), dim = (int)q.size(1);
+  long long blocks = (n_rows + 64 * ROWTILES - 1) / (64 * ROWTILES);
+  auto part = at::empty({blocks, n_q, k}, best.options());
+  auto* ip = reinterpret_cast<const elem*>(index.data_ptr());
+  auto* q_base = reinterpret_cast<const elem*>(q.data_ptr());
+  auto* part_p = reinterpret_cast<unsigned long long*>(part.data_ptr<int64_t>());
+  auto* best_p = reinterpret_cast<unsigned long long*>(best.data_ptr<int64_t>());
+  auto launch = [&](auto kernel, int qb) {
+    // query block + wave lists (+ q_scope stage)
+    size_t lds_bytes = (size_t)qb * (dim + E::kPad) * sizeof(elem) +
+                       (size_t)4 * qb * kbest_list_stride(k) * 8 + (SCOPED ? qb * 8 : 0);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, kKbestLdsLimit);
+    for (int q0 = 0; q0 < n_q; q0 += qb)
+      hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), lds_bytes,
+                         current_stream(), ip, n_rows, q_base + (long long)q0 * dim,
+                         std::min(qb, n_q - q0), dim, k, part_p + (long long)q0 * k,
+                         (long long)n_q * k, rs, re, SCOPED ? qsc + q0 : nullptr, now);
+  };
+  switch (dim >> 5) {
+    case 12:
+      launch(&cache_topk_k_kernel_t<E, 12, ROWTILES, SCOPED>, 16 * kbest_qtiles<E, 12>());
+      break;
+    case 8:
+      launch(&cache_topk_k_kernel_t<E, 8, ROWTILES, SCOPED>, 16 * kbest_qtiles<E, 8>());
+      break;
+    case 16:
+      launch(&cache_topk_k_kernel_t<E, 16, ROWTILES, SCOPED>, 16 * kbest_qtiles<E, 16>());
+      break;
+    case 4:
+      launch(&cache_topk_k_kernel_t<E, 4, ROWTILES, SCOPED>, 16 * kbest_qtiles<E, 4>());
+      break;
+    default:
+      TORCH_CHECK(false, "cache_topk_k: unsupported dim ", dim,
+                  " (supported: 128/256/384/512)");
+  }
+  hipLaunchKernelGGL(cache_topk_k_merge_kernel<kKbestMax>, dim3((unsigned)((n_q + 3) / 4)),
+                     dim3(256), 0, current_stream(), part_p, blocks, n_q, k, best_p);
+}
+
+// (hi int64 [n_q, k], idx int32 [n_q, k]) in cache_topk_scoped's encoding,
+// each row sorted by descending key; idx -1 / hi 0 past the last eligible
+// row. The three tag tensors come together or not at all.
+std::vector<at::Tensor> cache_topk_k(at::Tensor index, at::Tensor q, int64_t k,
+                                     c10::optional<at::Tensor> row_scope,
+                                     c10::optional<at::Tensor> row_expiry,
+                                     c10::optional<at::Tensor> q_scope, int64_t now) {
+  check_cuda(index, "index");
+  check_cuda(q, "q");
+  bool scoped = row_scope.has_value();
+  TORCH_CHECK(row_expiry.has_value() == scoped && q_scope.has_value() == scoped,
+              "cache_topk_k: row_scope, row_expiry and q_scope are given together or "
+              "not at all");
+  bool fp8 = index.scalar_type() == at::kFloat8_e4m3fn;
+  TORCH_CHECK(index.scalar_type() == q.scalar_type(), "index/q dtype mismatch");
+  TORCH_CHECK(fp8 || index.scalar_type() == at::kBFloat16,
+              "bf16 or float8_e4m3fn required");
+  TORCH_CHECK(index.dim() == 2 && q.dim() == 2, "index and q must be 2-D");
+  TORCH_CHECK(index.is_contiguous() && q.is_contiguous(),
+              "cache_topk_k: index and q must be contiguous");
+  long long n_rows = index.size(0);
+  int n_q = (int)q.size(0), dim = (int)q.size(1);
+  TORCH_CHECK(index.size(1) == dim, "dim mismatch");
+  TORCH_CHECK(dim % 32 == 0 && dim <= 512, "dim must be a multiple of 32, <= 512");
+  TORCH_CHECK(n_q <= 256, "cache_topk_k: at most 256 queries per call");
+  TORCH_CHECK(k >= 1 && k <= kKbestMax, "cache_topk_k: k must be in [1, ", kKbestMax,
+              "], got ", k);
+  TORCH_CHECK(q.device() == index.device(),
+              "cache_topk_k: all tensors must be on one device");
+  const long long *rs = nullptr, *qsc = nullptr;
+  const int* re = nullptr;
+  if (scoped) {
+    check_cuda(*row_scope, "row_scope");
+    check_cuda(*row_expiry, "row_expiry");
+    check_cuda(*q_scope, "q_scope");
+    TORCH_CHECK(row_scope->scalar_type() == at::kLong && row_scope->dim() == 1 &&
+                    row_scope->size(0) == n_rows,
+                "row_scope must be int64[n_rows]");
+    TORCH_CHECK(row_expiry->scalar_type() == at::kInt && row_expiry->dim() == 1 &&
+                    row_expiry->size(0) == n_rows,
+                "row_expiry must be int32[n_rows]");
+    TORCH_CHECK(q_scope->scalar_type() == at::kLong && q_scope->dim() == 1 &&
+                    q_scope->size(0) == n_q,
+                "q_scope must be int64[n_q]");
+    TORCH_CHECK(row_scope->device() == index.device() &&
+                    row_expiry->device() == index.device() &&
+                    q_scope->device() == index.device(),
+                "cache_topk_k: all tensors must be on one device");
+    TORCH_CHECK(row_scope->is_contiguous() && row_expiry->is_contiguous() &&
+                    q_scope->is_contiguous(),
+                "cache_topk_k: tag tensors must be contiguous");
+    // the kernel reads a lane's 4 row tags as 16-byte vectors
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(row_scope->data_ptr()) % 32 == 0 &&
+                    reinterpret_cast<uintptr_t>(row_expiry->data_ptr()) % 16 == 0,
+                "row_scope/row_expiry must start 32/16-byte aligned (row 4k of the "
+                "allocation)");
+    TORCH_CHECK(now >= INT32_MIN && now <= INT32_MAX, "now must fit int32");
+    rs = reinterpret_cast<const long long*>(row_scope->data_ptr<int64_t>());
+    re = row_expiry->data_ptr<int32_t>();
+    qsc = reinterpret_cast<const long long*>(q_scope->data_ptr<int64_t>());
+  }
+  auto best = at::zeros({n_q, k}, at::TensorOptions().dtype(at::kLong).device(q.device()));
+  if (n_q == 0 || n_rows == 0)
+    return {best, at::full({n_q, k}, -1, best.options().dtype(at::kInt))};
+  int kk = (int)k, nw = scoped ? (int)now : 0;
+  if (fp8 && scoped)
+    launch_cache_topk_k<CacheElemFp8, true>(index, q, kk, rs, re, qsc, nw, best);
+  else if (fp8)
+    launch_cache_topk_k<CacheElemFp8, false>(index, q, kk, rs, re, qsc, nw, best);
+  else if (scoped)
+    launch_cache_topk_k<CacheElemBf16, true>(index, q, kk, rs, re, qsc, nw, best);
+  else
+    launch_cache_topk_k<CacheElemBf16, false>(index, q, kk, rs, re, qsc, nw, best);
   auto hi = best.bitwise_right_shift(32).to(at::kLong);
   auto idx = at::where(best == 0, -1, best.bitwise_and(0xFFFFFFFFLL)).to(at::kInt);
   return {hi, idx};
@@ -1000,6 +1135,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "cache_topk, row_scope must start 32-byte and row_expiry 16-byte "
         "aligned (the kernel reads 4 row tags as 16-byte vectors): pass "
         "tensors sliced from row 4k of their allocation, not e.g. row_scope[1:].");
+  m.def("cache_topk_k", &cache_topk_k,
+        "The k (1..8) best rows per query, fused into the index scan: (hi int64 "
+        "[n_q, k], idx int32 [n_q, k]), each row by descending score, the higher "
+        "index row first among equal scores; idx -1 / hi 0 past the last "
+        "eligible row. With row_scope, row_expiry and q_scope (all three or "
+        "none) rows are filtered and aligned as in cache_topk_scoped.",
+        py::arg("index"), py::arg("q"), py::arg("k"), py::arg("row_scope") = py::none(),
+        py::arg("row_expiry") = py::none(), py::arg("q_scope") = py::none(),
+        py::arg("now") = 0);
   m.def("mxfp4_quantize_rows", &mxfp4_quantize_rows,
         "bf16 [n, dim] -> (packed e2m1 nibbles u8 [n, dim/2], E8M0 scale u8 "
         "[n, dim/32], inv_norm f32 [n]); the format of aigw/ops/mxfp4_ref.py");

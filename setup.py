@@ -21,6 +21,7 @@ from torch.utils.cpp_extension import BuildExtension, CUDAExtension  # noqa: E40
 HIP_HEADERS = [
     "csrc/bpe_kernels.cuh",
     "csrc/cache_kernels.cuh",
+    "csrc/cache_kbest_kernels.cuh",
     "csrc/mxfp4_kernels.cuh",
     "csrc/prefix_kernels.cuh",
 ]
