@@ -88,6 +88,7 @@ async def _run_shard(args, rank: int = 0, world: int = 1) -> None:
             gpu_services = GPUServices(
                 device=f"cuda:{rank}", enable_cache=args.semantic_cache,
                 cache_index_dtype=getattr(args, "cache_index_dtype", "bf16"),
+                cache_dim=getattr(args, "cache_dim", 384),
                 cache_scoped=getattr(args, "cache_scope", "value") == "index",
                 cache_ttl_s=getattr(args, "cache_ttl_s", 0) or None,
                 cache_candidates=getattr(args, "cache_candidates", 1),
@@ -268,6 +269,27 @@ def _check_cache_flags(args) -> None:
     candidates = getattr(args, "cache_candidates", 1)
     if not 1 <= candidates <= 8:
         raise SystemExit("--semantic-cache-candidates must be 1..8")
+    dim = getattr(args, "cache_dim", 384)
+    if dim % 128 or not 128 <= dim <= 1024:
+        raise SystemExit(
+            f"--semantic-cache-dim must be a multiple of 128 in 128..1024 (the "
+            f"widths the built-in embedder feeds), got {dim}")
+    if dim != 384 and args.front == "fast" and args.gpu and args.semantic_cache:
+        raise SystemExit(
+            "--semantic-cache-dim other than 384 is not supported by the native "
+            "front (--front fast): its in-process cache is fixed at 384 — use "
+            "--front lean")
+    if dim > 512 and args.gpu and args.semantic_cache:
+        if getattr(args, "cache_index_dtype", "bf16") == "mxfp4":
+            raise SystemExit(
+                "--semantic-cache-dim above 512 is not supported with "
+                "--cache-index-dtype mxfp4: MXFP4 rows are 128..512 wide — use "
+                "bf16 or fp8")
+        if candidates > 1:
+            raise SystemExit(
+                "--semantic-cache-dim above 512 is not supported with "
+                "--semantic-cache-candidates above 1: the k-best lookup kernel "
+                "serves rows up to 512 wide")
     if candidates > 1 and args.gpu and args.semantic_cache:
         if args.front == "fast":
             # the native front's in-process lookup is the arg-max kernel
@@ -416,6 +438,13 @@ def main(argv=None) -> int:
                            "lookups, ~1%% cosine error; mxfp4 = 3.7x rows per GB at "
                            "dim 384, 4-bit MX blocks against fp8 queries, not served "
                            "by --front fast)")
+    runp.add_argument("--semantic-cache-dim", type=int, default=384, dest="cache_dim",
+                      metavar="N",
+                      help="semantic-cache embedding and index row width: a multiple "
+                           "of 128 in 128..1024 (768 and 1024 are the base and large "
+                           "embedding models' widths). Above 512 the wide-row lookup "
+                           "kernel serves it: bf16/fp8 index, one candidate per lookup; "
+                           "--front fast is fixed at 384")
     runp.add_argument("--semantic-cache-scope", choices=["value", "index"],
                       default="value", dest="cache_scope",
                       help="where a cached answer's scope (model, route, sampling "

@@ -82,6 +82,9 @@ class GPUServices:
         n_merges: int = 32768,
         enable_cache: bool = False,
         cache_capacity: int = 65536,
+        # index row width: a multiple of 128 up to 1024 (what the built-in
+        # embedder feeds); above 512 bf16/fp8 only, one candidate per lookup
+        cache_dim: int = 384,
         cache_threshold: float = 0.92,
         cache_index_dtype: str = "bf16",  # "bf16" | "fp8" (2x rows/GB, faster lookups)
         # | "mxfp4" (3.7x rows/GB at dim 384)
@@ -106,6 +109,7 @@ class GPUServices:
         self.cache: Optional[SemanticCache] = (
             SemanticCache(
                 self.tokenizer.vocab_size,
+                dim=cache_dim,
                 capacity=cache_capacity,
                 threshold=cache_threshold,
                 device=device,

@@ -5,6 +5,10 @@ The embedding pipeline (mean-pooled token embeddings → bf16 MFMA projection
 output. The index is a ring buffer of bf16 rows sized for the 288 GB HBM3E
 budget; lookup is the fused MFMA similarity + argmax kernel (one pass over
 the index, no materialized score matrix).
+
+Index rows are 128..512 wide (the arg-max kernels, every index dtype) or, for
+bf16 and fp8 indexes, a multiple of 128 up to 2048 (cache_topk_wide: 768,
+1024, 1536 and 2048 are the widths of the common embedding models).
 """
 
 from __future__ import annotations
@@ -22,6 +26,9 @@ from aigw.ops import load_hip_module
 NEVER = 0x7FFFFFFF  # row_expiry of a row without a TTL
 
 INDEX_DTYPES = {"bf16": torch.bfloat16, "fp8": torch.float8_e4m3fn, "mxfp4": torch.uint8}
+
+NARROW_MAX_DIM = 512  # widest row of cache_topk, cache_topk_scoped and cache_topk_k
+WIDE_MAX_DIM = 2048  # widest row of cache_topk_wide
 
 
 def scope_id(b: bytes) -> int:
@@ -78,6 +85,12 @@ class SemanticCache:
             raise ValueError(
                 f"index_dtype must be one of {', '.join(INDEX_DTYPES)}, got {index_dtype!r}")
         self.mxfp4 = index_dtype == "mxfp4"
+        # rows past 512 elements are looked up by cache_topk_wide
+        self.wide = dim > NARROW_MAX_DIM
+        if self.wide and not self.mxfp4 and (dim % 128 or dim > WIDE_MAX_DIM):
+            raise ValueError(
+                f"dim above {NARROW_MAX_DIM} must be a multiple of 128, at most "
+                f"{WIDE_MAX_DIM}, got {dim}")
         # dtype of the stored rows; mxfp4 rows are packed nibbles
         self.index_dtype = INDEX_DTYPES[index_dtype]
         # dtype the lookup kernels take queries in
@@ -116,7 +129,11 @@ class SemanticCache:
         self.record_pending = False
 
     def embed(self, out_ids: torch.Tensor, req_off: torch.Tensor) -> torch.Tensor:
-        """(B, dim) bf16 L2-normalized query vectors from tokenizer output."""
+        """(B, dim) bf16 L2-normalized query vectors from tokenizer output.
+
+        The built-in embedder stops at dim 1024 (meanpool's limit); a cache
+        with wider rows takes its callers' own vectors in ``insert`` and
+        ``lookup``."""
         pooled = self.hip.meanpool(out_ids, req_off, self.emb)  # fp32 (B, dim)
         pooled_bf = pooled.to(torch.bfloat16)
         proj = self.hip.gemm_bf16_nt(pooled_bf, self.proj, None, False)  # fp32
@@ -174,6 +191,9 @@ class SemanticCache:
                     )
                 else:
                     h, i = self.hip.cache_topk_mxfp4(*rows, qs)
+            elif self.wide:
+                tags = (row_scope, row_expiry, q_scope[q0 : q0 + 256], now) if filtering else ()
+                h, i = self.hip.cache_topk_wide(view, qs, *tags)
             elif filtering:
                 h, i = self.hip.cache_topk_scoped(
                     view, qs, row_scope, row_expiry, q_scope[q0 : q0 + 256], now
@@ -184,7 +204,7 @@ class SemanticCache:
             idx.extend(i.cpu().tolist())
         out = []
         for h, i in zip(hi, idx):
-            if i < 0:  # scoped lookup: no row this query may see
+            if i < 0:  # scoped or wide lookup: no row this query may see
                 out.append(None)
                 continue
             score = _unorder(h)
@@ -209,6 +229,10 @@ class SemanticCache:
             raise ValueError(
                 "lookup_k: k-best lookup is not implemented for index_dtype='mxfp4' "
                 "(bf16 and fp8 only)")
+        if self.wide:
+            raise ValueError(
+                f"lookup_k: k-best lookup serves dim <= {NARROW_MAX_DIM}, this cache "
+                f"has dim {self.dim}")
         n = queries.shape[0]
         if self.size == 0:
             return [[] for _ in range(n)]

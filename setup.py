@@ -22,6 +22,7 @@ HIP_HEADERS = [
     "csrc/bpe_kernels.cuh",
     "csrc/cache_kernels.cuh",
     "csrc/cache_kbest_kernels.cuh",
+    "csrc/cache_wide_kernels.cuh",
     "csrc/mxfp4_kernels.cuh",
     "csrc/prefix_kernels.cuh",
 ]
