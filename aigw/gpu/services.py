@@ -83,11 +83,11 @@ class GPUServices:
         enable_cache: bool = False,
         cache_capacity: int = 65536,
         # index row width: a multiple of 128 up to 1024 (what the built-in
-        # embedder feeds); above 512 bf16/fp8 only, one candidate per lookup
+        # embedder feeds), every index dtype; above 512 one candidate per lookup
         cache_dim: int = 384,
         cache_threshold: float = 0.92,
         cache_index_dtype: str = "bf16",  # "bf16" | "fp8" (2x rows/GB, faster lookups)
-        # | "mxfp4" (3.7x rows/GB at dim 384)
+        # | "mxfp4" (3.7x rows/GB: 208 B per dim-384 row, 548 B per dim-1024 row)
         cache_scoped: bool = False,  # filter cache rows by scope in the index
         cache_ttl_s: Optional[float] = None,  # None: cached rows never expire
         # index rows fetched per lookup (1..8); above 1 a caller can walk

@@ -6,9 +6,10 @@ output. The index is a ring buffer of bf16 rows sized for the 288 GB HBM3E
 budget; lookup is the fused MFMA similarity + argmax kernel (one pass over
 the index, no materialized score matrix).
 
-Index rows are 128..512 wide (the arg-max kernels, every index dtype) or, for
-bf16 and fp8 indexes, a multiple of 128 up to 2048 (cache_topk_wide: 768,
-1024, 1536 and 2048 are the widths of the common embedding models).
+Index rows are 128..512 wide (the arg-max kernels, every index dtype) or a
+multiple of 128 up to 2048 (cache_topk_wide for bf16 and fp8 indexes,
+cache_topk_mxfp4_wide for mxfp4: 768, 1024, 1536 and 2048 are the widths of
+the common embedding models). An mxfp4 index takes multiples of 128 only.
 """
 
 from __future__ import annotations
@@ -55,7 +56,8 @@ class SemanticCache:
         # HBM per row -> 2x rows in the 288 GB budget, 2x lookup bandwidth;
         # ~1% cosine error from 3-bit mantissas averaged over 384 dims)
         # | "mxfp4" (OCP MX e2m1 blocks against fp8 queries: 208 B per
-        # dim-384 row, 3.7x the rows of bf16; aigw/ops/mxfp4_ref.py)
+        # dim-384 row, 548 B per dim-1024 row, 3.7x the rows of bf16; dim a
+        # multiple of 128 in 128..2048; aigw/ops/mxfp4_ref.py)
         _hip=None,
         *,
         scoped: bool = False,  # lookups filter rows by scope inside the kernel
@@ -85,7 +87,8 @@ class SemanticCache:
             raise ValueError(
                 f"index_dtype must be one of {', '.join(INDEX_DTYPES)}, got {index_dtype!r}")
         self.mxfp4 = index_dtype == "mxfp4"
-        # rows past 512 elements are looked up by cache_topk_wide
+        # rows past 512 elements are looked up by cache_topk_wide, or by
+        # cache_topk_mxfp4_wide in an mxfp4 index
         self.wide = dim > NARROW_MAX_DIM
         if self.wide and not self.mxfp4 and (dim % 128 or dim > WIDE_MAX_DIM):
             raise ValueError(
@@ -96,9 +99,10 @@ class SemanticCache:
         # dtype the lookup kernels take queries in
         self.query_dtype = torch.float8_e4m3fn if self.mxfp4 else self.index_dtype
         if self.mxfp4:
-            if dim % 128 or not 128 <= dim <= 512:
+            if dim % 128 or not 128 <= dim <= WIDE_MAX_DIM:
                 raise ValueError(
-                    f"index_dtype='mxfp4' needs dim 128, 256, 384 or 512, got {dim}")
+                    f"index_dtype='mxfp4' needs dim a multiple of 128 in "
+                    f"128..{WIDE_MAX_DIM}, got {dim}")
             self.index = torch.zeros(capacity, dim // 2, dtype=torch.uint8, device=self.device)
             # one E8M0 scale byte per 32 elements, and 1/|dequantised row|
             self.index_scale = torch.full((capacity, dim // 32), 127, dtype=torch.uint8,
@@ -185,7 +189,11 @@ class SemanticCache:
             qs = queries[q0 : q0 + 256].to(self.query_dtype).contiguous()
             if self.mxfp4:
                 rows = (view, self.index_scale[: self.size], self.index_inv_norm[: self.size])
-                if filtering:
+                if self.wide:
+                    tags = ((row_scope, row_expiry, q_scope[q0 : q0 + 256], now)
+                            if filtering else ())
+                    h, i = self.hip.cache_topk_mxfp4_wide(*rows, qs, *tags)
+                elif filtering:
                     h, i = self.hip.cache_topk_mxfp4_scoped(
                         *rows, qs, row_scope, row_expiry, q_scope[q0 : q0 + 256], now
                     )

@@ -71,6 +71,12 @@ static inline hipStream_t current_stream() {
 #include "mxfp4_kernels.cuh"
 
 // ---------------------------------------------------------------------------
+// 3c'. MXFP4 index, wide rows (dim 640..2048): K-chunked scaled-MFMA lookup
+// ---------------------------------------------------------------------------
+
+#include "mxfp4_wide_kernels.cuh"
+
+// ---------------------------------------------------------------------------
 // 5. Prefix-cache-aware endpoint picking (block hashes, HBM block index)
 // ---------------------------------------------------------------------------
 
@@ -763,8 +769,8 @@ std::vector<at::Tensor> mxfp4_quantize_rows(at::Tensor x) {
               "mxfp4_quantize_rows: bf16 [n, dim] required");
   long long n = x.size(0);
   int dim = (int)x.size(1);
-  TORCH_CHECK(dim % 128 == 0 && dim >= 128 && dim <= 512,
-              "mxfp4_quantize_rows: dim must be 128, 256, 384 or 512, got ", dim);
+  TORCH_CHECK(dim % 128 == 0 && dim >= 128 && dim <= kWideMaxDim,
+              "mxfp4_quantize_rows: dim must be a multiple of 128 in 128..2048, got ", dim);
   TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
               "mxfp4_quantize_rows: x must start 16-byte aligned");
   auto u8 = at::TensorOptions().dtype(at::kByte).device(x.device());
@@ -772,8 +778,10 @@ std::vector<at::Tensor> mxfp4_quantize_rows(at::Tensor x) {
   at::Tensor scale = at::empty({n, dim / 32}, u8);
   at::Tensor inv_norm = at::empty({n}, u8.dtype(at::kFloat));
   if (n == 0) return {packed, scale, inv_norm};
-  hipLaunchKernelGGL(mxfp4_quantize_rows_kernel, dim3((unsigned)((n + 3) / 4)),
-                     dim3(256), 0, current_stream(),
+  // one wave per row either way; rows past 512 elements take the slab kernel
+  auto kernel = dim <= kMxQuantSlab ? mxfp4_quantize_rows_kernel
+                                    : mxfp4_quantize_rows_wide_kernel;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, current_stream(),
                      reinterpret_cast<const bf16*>(x.data_ptr<at::BFloat16>()), n, dim,
                      packed.data_ptr<uint8_t>(), scale.data_ptr<uint8_t>(),
                      inv_norm.data_ptr<float>());
@@ -891,6 +899,125 @@ std::vector<at::Tensor> cache_topk_mxfp4_scoped(at::Tensor packed, at::Tensor sc
                                                 at::Tensor q_scope, int64_t now) {
   return cache_topk_mxfp4_impl<true>("cache_topk_mxfp4_scoped", packed, scale, inv_norm, q,
                                      &row_scope, &row_expiry, &q_scope, now);
+}
+
+// Wide MXFP4 rows (mxfp4_wide_kernels.cuh): passes of the fp8 query block's
+// wide_queries_per_pass queries, each one launch that streams the whole index.
+template <bool SCOPED>
+static void launch_cache_topk_mxfp4_wide(const at::Tensor& packed, const at::Tensor& scale,
+                                         const at::Tensor& inv_norm, const at::Tensor& q,
+                                         const long long* rs, const int* re,
+                                         const long long* qsc, int now, at::Tensor& best) {
+  long long n_rows = packed.size(0);
+  int n_q = (int)q.size(0), dim = (int)q.size(1);
+  long long blocks = (n_rows + 64 * kMxWideRowTiles - 1) / (64 * kMxWideRowTiles);
+  auto* q_base = reinterpret_cast<const uint8_t*>(q.data_ptr());
+  auto* best_p = reinterpret_cast<unsigned long long*>(best.data_ptr<int64_t>());
+  auto kernel = &cache_topk_mxfp4_wide_kernel_t<SCOPED>;
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, kWideLdsLimit);
+  const int qb = wide_queries_per_pass<CacheElemFp8, SCOPED>(dim);
+  for (int q0 = 0; q0 < n_q; q0 += qb) {
+    int kq = std::min(qb, n_q - q0);
+    size_t lds_bytes = wide_lds_bytes<CacheElemFp8, SCOPED>(dim, kq);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), lds_bytes,
+                       current_stream(), packed.data_ptr<uint8_t>(),
+                       scale.data_ptr<uint8_t>(), inv_norm.data_ptr<float>(), n_rows,
+                       q_base + (long long)q0 * dim, kq, dim, best_p + q0, rs, re,
+                       SCOPED ? qsc + q0 : nullptr, now);
+  }
+}
+
+// cache_topk_mxfp4_scoped's (hi, idx) for rows of 640..2048 elements; without
+// the three tag tensors every row is eligible. idx -1 / hi 0: no row may answer.
+std::vector<at::Tensor> cache_topk_mxfp4_wide(at::Tensor packed, at::Tensor scale,
+                                              at::Tensor inv_norm, at::Tensor q,
+                                              c10::optional<at::Tensor> row_scope,
+                                              c10::optional<at::Tensor> row_expiry,
+                                              c10::optional<at::Tensor> q_scope,
+                                              int64_t now) {
+  const char* op = "cache_topk_mxfp4_wide";
+  check_cuda(packed, "packed");
+  check_cuda(scale, "scale");
+  check_cuda(inv_norm, "inv_norm");
+  check_cuda(q, "q");
+  bool scoped = row_scope.has_value();
+  TORCH_CHECK(row_expiry.has_value() == scoped && q_scope.has_value() == scoped, op,
+              ": row_scope, row_expiry and q_scope are given together or not at all");
+  TORCH_CHECK(q.scalar_type() == at::kFloat8_e4m3fn && q.dim() == 2, op,
+              ": q must be float8_e4m3fn [n_q, dim]");
+  int n_q = (int)q.size(0);
+  long long dim = q.size(1);
+  TORCH_CHECK(dim % 128 == 0 && dim > 512 && dim <= kWideMaxDim, op,
+              ": dim must be a multiple of 128 in 640..2048, got ", dim,
+              " (128..512: cache_topk_mxfp4, cache_topk_mxfp4_scoped)");
+  TORCH_CHECK(packed.scalar_type() == at::kByte && packed.dim() == 2 &&
+                  packed.size(1) == dim / 2,
+              op, ": packed must be uint8 [n_rows, dim/2]");
+  long long n_rows = packed.size(0);
+  TORCH_CHECK(scale.scalar_type() == at::kByte && scale.dim() == 2 &&
+                  scale.size(0) == n_rows && scale.size(1) == dim / 32,
+              op, ": scale must be uint8 [n_rows, dim/32]");
+  TORCH_CHECK(inv_norm.scalar_type() == at::kFloat && inv_norm.dim() == 1 &&
+                  inv_norm.size(0) == n_rows,
+              op, ": inv_norm must be float32 [n_rows]");
+  TORCH_CHECK(n_q <= 256, op, ": at most 256 queries per call");
+  TORCH_CHECK(scale.device() == packed.device() && inv_norm.device() == packed.device() &&
+                  q.device() == packed.device(),
+              op, ": all tensors must be on one device");
+  TORCH_CHECK(packed.is_contiguous() && scale.is_contiguous() && inv_norm.is_contiguous() &&
+                  q.is_contiguous(),
+              op, ": packed, scale, inv_norm and q must be contiguous");
+  // 16-byte row and query fragments, a dword of scale bytes per k-step,
+  // 16 bytes of inv_norm per 4 result rows
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(packed.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(scale.data_ptr()) % 4 == 0 &&
+                  reinterpret_cast<uintptr_t>(inv_norm.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              op, ": packed/inv_norm/q must start 16-byte and scale 4-byte aligned");
+  const long long *rs = nullptr, *qsc = nullptr;
+  const int* re = nullptr;
+  if (scoped) {
+    check_cuda(*row_scope, "row_scope");
+    check_cuda(*row_expiry, "row_expiry");
+    check_cuda(*q_scope, "q_scope");
+    TORCH_CHECK(row_scope->scalar_type() == at::kLong && row_scope->dim() == 1 &&
+                    row_scope->size(0) == n_rows,
+                "row_scope must be int64[n_rows]");
+    TORCH_CHECK(row_expiry->scalar_type() == at::kInt && row_expiry->dim() == 1 &&
+                    row_expiry->size(0) == n_rows,
+                "row_expiry must be int32[n_rows]");
+    TORCH_CHECK(q_scope->scalar_type() == at::kLong && q_scope->dim() == 1 &&
+                    q_scope->size(0) == n_q,
+                "q_scope must be int64[n_q]");
+    TORCH_CHECK(row_scope->device() == packed.device() &&
+                    row_expiry->device() == packed.device() &&
+                    q_scope->device() == packed.device(),
+                op, ": all tensors must be on one device");
+    TORCH_CHECK(row_scope->is_contiguous() && row_expiry->is_contiguous() &&
+                    q_scope->is_contiguous(),
+                op, ": tag tensors must be contiguous");
+    // the kernel reads a lane's 4 row tags as 16-byte vectors
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(row_scope->data_ptr()) % 32 == 0 &&
+                    reinterpret_cast<uintptr_t>(row_expiry->data_ptr()) % 16 == 0,
+                "row_scope/row_expiry must start 32/16-byte aligned (row 4k of the "
+                "allocation)");
+    TORCH_CHECK(now >= INT32_MIN && now <= INT32_MAX, "now must fit int32");
+    rs = reinterpret_cast<const long long*>(row_scope->data_ptr<int64_t>());
+    re = row_expiry->data_ptr<int32_t>();
+    qsc = reinterpret_cast<const long long*>(q_scope->data_ptr<int64_t>());
+  }
+  auto best = at::zeros({n_q}, at::TensorOptions().dtype(at::kLong).device(q.device()));
+  if (n_q == 0 || n_rows == 0)
+    return {best, at::full({n_q}, -1, best.options().dtype(at::kInt))};
+  if (scoped)
+    launch_cache_topk_mxfp4_wide<true>(packed, scale, inv_norm, q, rs, re, qsc, (int)now,
+                                       best);
+  else
+    launch_cache_topk_mxfp4_wide<false>(packed, scale, inv_norm, q, rs, re, qsc, 0, best);
+  auto hi = best.bitwise_right_shift(32).to(at::kLong);
+  auto idx = at::where(best == 0, -1, best.bitwise_and(0xFFFFFFFFLL)).to(at::kInt);
+  return {hi, idx};
 }
 
 at::Tensor kv_score_assign(at::Tensor stats, at::Tensor pred_tokens, double w_kv,
@@ -1269,13 +1396,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("now") = 0);
   m.def("mxfp4_quantize_rows", &mxfp4_quantize_rows,
         "bf16 [n, dim] -> (packed e2m1 nibbles u8 [n, dim/2], E8M0 scale u8 "
-        "[n, dim/32], inv_norm f32 [n]); the format of aigw/ops/mxfp4_ref.py");
+        "[n, dim/32], inv_norm f32 [n]), dim a multiple of 128 in 128..2048; the "
+        "format of aigw/ops/mxfp4_ref.py");
   m.def("cache_topk_mxfp4", &cache_topk_mxfp4,
         "cache_topk over an MXFP4 index (mxfp4_quantize_rows output) with "
         "float8_e4m3fn queries: score = (row . q) * inv_norm[row]");
   m.def("cache_topk_mxfp4_scoped", &cache_topk_mxfp4_scoped,
         "cache_topk_mxfp4 under the row filter of cache_topk_scoped; idx -1 / "
         "hi 0 for a query no row may answer");
+  m.def("cache_topk_mxfp4_wide", &cache_topk_mxfp4_wide,
+        "cache_topk_mxfp4 over rows of 640..2048 elements (a multiple of 128): the "
+        "best row per query, the higher row among equal scores; idx -1 / hi 0 where "
+        "no row is eligible. With row_scope, row_expiry and q_scope (all three or "
+        "none) rows are filtered and aligned as in cache_topk_scoped; without them "
+        "every row is eligible.",
+        py::arg("packed"), py::arg("scale"), py::arg("inv_norm"), py::arg("q"),
+        py::arg("row_scope") = py::none(), py::arg("row_expiry") = py::none(),
+        py::arg("q_scope") = py::none(), py::arg("now") = 0);
   m.def("kv_score_assign", &kv_score_assign, "greedy KV-occupancy assignment");
   m.def("prefix_block_hashes", &prefix_block_hashes,
         "chained token-block hashes per request: (hashes int64[n_req, max_blocks], "

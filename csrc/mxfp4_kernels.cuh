@@ -82,6 +82,79 @@ mxfp4_quantize_rows_kernel(const bf16* __restrict__ x, long long n, int dim,
   if (lane == 0) inv_norm[r] = ss > 0.f ? ldexpf(rsqrtf(ss), -emax) : 0.f;
 }
 
+// Wide rows: dim a multiple of 128 in 640..2048. Still one wave per row; the
+// row is cut into slabs of 512 elements and lane l owns elements 8l..8l+7 of
+// every slab, so a row is at most 4 short8 per lane and MX block b of a slab
+// is lanes 4b..4b+3 as above. The last slab may be partial (640 = 512 + 128):
+// a lane with s * 512 + 8l >= dim is off for that slab. The row-wide emax is
+// reduced over every slab before any square is summed, and the squares of all
+// slabs run down one fma chain per lane, so the arithmetic discipline of the
+// kernel above holds here too. A sibling: the kernel above does not move.
+constexpr int kMxQuantSlab = 512;
+constexpr int kMxQuantMaxSlabs = 4;
+
+__global__ void __launch_bounds__(256)
+mxfp4_quantize_rows_wide_kernel(const bf16* __restrict__ x, long long n, int dim,
+                                uint8_t* __restrict__ packed, uint8_t* __restrict__ scale,
+                                float* __restrict__ inv_norm) {
+  long long r = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
+  if (r >= n) return;  // wave-uniform
+  int lane = threadIdx.x & 63;
+  short8 raw[kMxQuantMaxSlabs];
+  int e[kMxQuantMaxSlabs];
+  int emax = -1000;
+  #pragma unroll
+  for (int s = 0; s < kMxQuantMaxSlabs; ++s) {
+    raw[s] = short8{0, 0, 0, 0, 0, 0, 0, 0};
+    e[s] = 0;
+    if (s * kMxQuantSlab >= dim) continue;  // wave-uniform: the row has no such slab
+    bool on = s * kMxQuantSlab + lane * 8 < dim;
+    if (on)
+      raw[s] = *reinterpret_cast<const short8*>(&x[r * dim + s * kMxQuantSlab + lane * 8]);
+    int am = 0;
+    #pragma unroll
+    for (int j = 0; j < 8; ++j) am = max(am, (int)raw[s][j] & 0x7FFF);
+    am = max(am, __shfl_xor(am, 1));
+    am = max(am, __shfl_xor(am, 2));
+    // the scale rule of mxfp4_quantize_rows_kernel
+    int es = (am >> 7) - 127 - ((am & 0x7F) <= 0x40 ? 2 : 1);
+    es = max(es, -127);
+    if (am == 0) es = 0;
+    e[s] = es;
+    if (on && am) emax = max(emax, es);
+  }
+  #pragma unroll
+  for (int off = 1; off < 64; off <<= 1) emax = max(emax, __shfl_xor(emax, off));
+  float ss = 0.f;
+  #pragma unroll
+  for (int s = 0; s < kMxQuantMaxSlabs; ++s) {
+    if (s * kMxQuantSlab >= dim) continue;
+    bool on = s * kMxQuantSlab + lane * 8 < dim;
+    bool counts = emax > -1000 && e[s] - emax >= -60;
+    unsigned word = 0;
+    #pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      unsigned bits = (unsigned short)raw[s][j];
+      float a = ldexpf(__uint_as_float((bits & 0x7FFFu) << 16), -e[s]);  // exact
+      bool c1 = a > 0.25f, c2 = a >= 0.75f, c3 = a > 1.25f, c4 = a >= 1.75f;
+      bool c5 = a > 2.5f, c6 = a >= 3.5f, c7 = a > 5.f;
+      unsigned code = c1 + c2 + c3 + c4 + c5 + c6 + c7;
+      int twice = c1 + c2 + c3 + c4 + 2 * (c5 + c6) + 4 * c7;  // 2 * |e2m1 value|
+      word |= (code | ((bits >> 15) << 3)) << (4 * j);
+      float d = counts ? ldexpf((float)twice, e[s] - emax - 1) : 0.f;
+      ss = fmaf(d, d, ss);
+    }
+    if (on) {
+      long long el = s * kMxQuantSlab + lane * 8;  // the lane's first element
+      *reinterpret_cast<unsigned*>(&packed[r * (dim / 2) + el / 2]) = word;
+      if ((lane & 3) == 0) scale[r * (dim / 32) + el / 32] = (uint8_t)(e[s] + 127);
+    }
+  }
+  #pragma unroll
+  for (int off = 1; off < 64; off <<= 1) ss += __shfl_xor(ss, off);
+  if (lane == 0) inv_norm[r] = ss > 0.f ? ldexpf(rsqrtf(ss), -emax) : 0.f;
+}
+
 // ---------------------------------------------------------------------------
 // Lookup: best[q] = max over rows of pack_score(score, row),
 //   score = (fp4 row . fp8 query) * inv_norm[row],

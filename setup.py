@@ -24,6 +24,7 @@ HIP_HEADERS = [
     "csrc/cache_kbest_kernels.cuh",
     "csrc/cache_wide_kernels.cuh",
     "csrc/mxfp4_kernels.cuh",
+    "csrc/mxfp4_wide_kernels.cuh",
     "csrc/prefix_kernels.cuh",
 ]
 _here = os.path.dirname(os.path.abspath(__file__))
