@@ -7,7 +7,8 @@ budget; lookup is the fused MFMA similarity + argmax kernel (one pass over
 the index, no materialized score matrix).
 
 Index rows are 128..512 wide (the arg-max kernels, every index dtype) or a
-multiple of 128 up to 2048 (cache_topk_wide for bf16 and fp8 indexes,
+multiple of 128 up to 2048 (cache_topk_wide for bf16 and fp8 indexes, its
+one-pass sibling cache_topk_wide_tiled for the batches that measured faster,
 cache_topk_mxfp4_wide for mxfp4: 768, 1024, 1536 and 2048 are the widths of
 the common embedding models). An mxfp4 index takes multiples of 128 only.
 """
@@ -201,7 +202,10 @@ class SemanticCache:
                     h, i = self.hip.cache_topk_mxfp4(*rows, qs)
             elif self.wide:
                 tags = (row_scope, row_expiry, q_scope[q0 : q0 + 256], now) if filtering else ()
-                h, i = self.hip.cache_topk_wide(view, qs, *tags)
+                if self._wide_tiled_serves(qs.shape[0], filtering):
+                    h, i = self.hip.cache_topk_wide_tiled(view, qs, *tags)
+                else:
+                    h, i = self.hip.cache_topk_wide(view, qs, *tags)
             elif filtering:
                 h, i = self.hip.cache_topk_scoped(
                     view, qs, row_scope, row_expiry, q_scope[q0 : q0 + 256], now
@@ -218,6 +222,32 @@ class SemanticCache:
             score = _unorder(h)
             out.append((i, score) if score >= self.threshold else None)
         return out
+
+    def _wide_pass(self, filtering: bool) -> int:
+        """Queries one index pass of cache_topk_wide holds at this width."""
+        return self.hip.cache_wide_queries_per_pass(
+            self.dim, self.index_dtype == torch.float8_e4m3fn, filtering)
+
+    def _wide_tiled_serves(self, n_q: int, filtering: bool) -> bool:
+        """Whether cache_topk_wide_tiled (one index pass for any batch)
+        takes a slice of n_q queries instead of cache_topk_wide (one pass
+        per LDS-full of full-width queries). Only where it measured faster
+        by more than 3% in both sweeps at 1M rows, the bold rows of
+        profiles/cache_topk_wide_tiled.md. bf16: from 2 passes at dim >=
+        1536; below that only filtered, from 3 passes. fp8: at dim >= 1536
+        from 3 passes, and filtered at dim 1536 from 2. Everywhere else the
+        multi-pass kernel is level or faster. Measured were dim 768 / 1024
+        / 1536 / 2048 with 37 / 128 / 256 queries; the widths and pass
+        counts between them follow the next lower measured one, by
+        extrapolation, not measurement."""
+        passes = -(-n_q // self._wide_pass(filtering))
+        if self.index_dtype == torch.float8_e4m3fn:
+            if self.dim < 1536:
+                return False
+            return passes >= 3 or (filtering and self.dim < 2048 and passes == 2)
+        if self.dim >= 1536:
+            return passes >= 2
+        return filtering and passes >= 3
 
     def lookup_k(
         self, queries: torch.Tensor, k: int, scopes: Optional[list[int]] = None

@@ -63,6 +63,7 @@ static inline hipStream_t current_stream() {
 // ---------------------------------------------------------------------------
 
 #include "cache_wide_kernels.cuh"
+#include "cache_wide_tiled_kernels.cuh"
 
 // ---------------------------------------------------------------------------
 // 3c. MXFP4 cache index: row quantiser + block-scaled fp4 x fp8 MFMA lookup
@@ -761,6 +762,122 @@ std::vector<at::Tensor> cache_topk_wide(at::Tensor index, at::Tensor q,
   return {hi, idx};
 }
 
+// Wide rows, tiled (cache_wide_tiled_kernels.cuh): one launch for up to 256
+// queries, dynamic LDS sized by the call's query tiles.
+template <class E, bool SCOPED>
+static void launch_cache_topk_wide_tiled(const at::Tensor& index, const at::Tensor& q,
+                                         const long long* rs, const int* re,
+                                         const long long* qsc, int now, at::Tensor& best) {
+  using elem = typename E::elem;
+  long long n_rows = index.size(0);
+  int n_q = (int)q.size(0), dim = (int)q.size(1);
+  long long blocks = (n_rows + kWideTiledBlockRows - 1) / kWideTiledBlockRows;
+  auto kernel = &cache_topk_wide_tiled_kernel_t<E, SCOPED>;
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, kWideLdsLimit);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256),
+                     (size_t)wide_tiled_lds_bytes<SCOPED>(n_q), current_stream(),
+                     reinterpret_cast<const elem*>(index.data_ptr()), n_rows,
+                     reinterpret_cast<const elem*>(q.data_ptr()), n_q, dim,
+                     reinterpret_cast<unsigned long long*>(best.data_ptr<int64_t>()), rs, re,
+                     qsc, now);
+}
+
+// cache_topk_wide's arguments, checks and (hi, idx), from one pass over the
+// index for any n_q <= 256.
+std::vector<at::Tensor> cache_topk_wide_tiled(at::Tensor index, at::Tensor q,
+                                              c10::optional<at::Tensor> row_scope,
+                                              c10::optional<at::Tensor> row_expiry,
+                                              c10::optional<at::Tensor> q_scope, int64_t now) {
+  check_cuda(index, "index");
+  check_cuda(q, "q");
+  bool scoped = row_scope.has_value();
+  TORCH_CHECK(row_expiry.has_value() == scoped && q_scope.has_value() == scoped,
+              "cache_topk_wide_tiled: row_scope, row_expiry and q_scope are given together or "
+              "not at all");
+  bool fp8 = index.scalar_type() == at::kFloat8_e4m3fn;
+  TORCH_CHECK(index.scalar_type() == q.scalar_type(), "index/q dtype mismatch");
+  TORCH_CHECK(fp8 || index.scalar_type() == at::kBFloat16,
+              "bf16 or float8_e4m3fn required");
+  TORCH_CHECK(index.dim() == 2 && q.dim() == 2, "index and q must be 2-D");
+  TORCH_CHECK(index.is_contiguous() && q.is_contiguous(),
+              "cache_topk_wide_tiled: index and q must be contiguous");
+  long long n_rows = index.size(0);
+  int n_q = (int)q.size(0);
+  long long dim = q.size(1);
+  TORCH_CHECK(index.size(1) == dim, "dim mismatch");
+  TORCH_CHECK(dim % kWideChunk == 0 && dim > 512 && dim <= kWideMaxDim,
+              "cache_topk_wide_tiled: dim must be a multiple of 128 in 640..2048, got ", dim,
+              " (128..512: cache_topk, cache_topk_scoped)");
+  TORCH_CHECK(n_q <= 256, "cache_topk_wide_tiled: at most 256 queries per call");
+  TORCH_CHECK(q.device() == index.device(),
+              "cache_topk_wide_tiled: all tensors must be on one device");
+  // rows and queries are read as 16-byte vectors
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(index.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "cache_topk_wide_tiled: index and q must start 16-byte aligned");
+  const long long *rs = nullptr, *qsc = nullptr;
+  const int* re = nullptr;
+  if (scoped) {
+    check_cuda(*row_scope, "row_scope");
+    check_cuda(*row_expiry, "row_expiry");
+    check_cuda(*q_scope, "q_scope");
+    TORCH_CHECK(row_scope->scalar_type() == at::kLong && row_scope->dim() == 1 &&
+                    row_scope->size(0) == n_rows,
+                "row_scope must be int64[n_rows]");
+    TORCH_CHECK(row_expiry->scalar_type() == at::kInt && row_expiry->dim() == 1 &&
+                    row_expiry->size(0) == n_rows,
+                "row_expiry must be int32[n_rows]");
+    TORCH_CHECK(q_scope->scalar_type() == at::kLong && q_scope->dim() == 1 &&
+                    q_scope->size(0) == n_q,
+                "q_scope must be int64[n_q]");
+    TORCH_CHECK(row_scope->device() == index.device() &&
+                    row_expiry->device() == index.device() &&
+                    q_scope->device() == index.device(),
+                "cache_topk_wide_tiled: all tensors must be on one device");
+    TORCH_CHECK(row_scope->is_contiguous() && row_expiry->is_contiguous() &&
+                    q_scope->is_contiguous(),
+                "cache_topk_wide_tiled: tag tensors must be contiguous");
+    // the kernel reads a lane's 4 row tags as 16-byte vectors
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(row_scope->data_ptr()) % 32 == 0 &&
+                    reinterpret_cast<uintptr_t>(row_expiry->data_ptr()) % 16 == 0,
+                "row_scope/row_expiry must start 32/16-byte aligned (row 4k of the "
+                "allocation)");
+    TORCH_CHECK(now >= INT32_MIN && now <= INT32_MAX, "now must fit int32");
+    rs = reinterpret_cast<const long long*>(row_scope->data_ptr<int64_t>());
+    re = row_expiry->data_ptr<int32_t>();
+    qsc = reinterpret_cast<const long long*>(q_scope->data_ptr<int64_t>());
+  }
+  auto best = at::zeros({n_q}, at::TensorOptions().dtype(at::kLong).device(q.device()));
+  if (n_q == 0 || n_rows == 0)
+    return {best, at::full({n_q}, -1, best.options().dtype(at::kInt))};
+  int nw = scoped ? (int)now : 0;
+  if (fp8 && scoped)
+    launch_cache_topk_wide_tiled<CacheElemFp8, true>(index, q, rs, re, qsc, nw, best);
+  else if (fp8)
+    launch_cache_topk_wide_tiled<CacheElemFp8, false>(index, q, rs, re, qsc, nw, best);
+  else if (scoped)
+    launch_cache_topk_wide_tiled<CacheElemBf16, true>(index, q, rs, re, qsc, nw, best);
+  else
+    launch_cache_topk_wide_tiled<CacheElemBf16, false>(index, q, rs, re, qsc, nw, best);
+  auto hi = best.bitwise_right_shift(32).to(at::kLong);
+  auto idx = at::where(best == 0, -1, best.bitwise_and(0xFFFFFFFFLL)).to(at::kInt);
+  return {hi, idx};
+}
+
+// Queries one pass of cache_topk_wide holds: the constexpr its launch uses.
+int64_t cache_wide_queries_per_pass(int64_t dim, bool fp8, bool scoped) {
+  TORCH_CHECK(dim % kWideChunk == 0 && dim > 512 && dim <= kWideMaxDim,
+              "cache_wide_queries_per_pass: dim must be a multiple of 128 in 640..2048, got ",
+              dim);
+  int d = (int)dim;
+  if (fp8)
+    return scoped ? wide_queries_per_pass<CacheElemFp8, true>(d)
+                  : wide_queries_per_pass<CacheElemFp8, false>(d);
+  return scoped ? wide_queries_per_pass<CacheElemBf16, true>(d)
+                : wide_queries_per_pass<CacheElemBf16, false>(d);
+}
+
 // MXFP4 index rows from bf16 vectors: (packed u8 [n, dim/2], scale u8
 // [n, dim/32], inv_norm f32 [n]), bit-identical to aigw/ops/mxfp4_ref.py.
 std::vector<at::Tensor> mxfp4_quantize_rows(at::Tensor x) {
@@ -1394,6 +1511,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("index"), py::arg("q"), py::arg("row_scope") = py::none(),
         py::arg("row_expiry") = py::none(), py::arg("q_scope") = py::none(),
         py::arg("now") = 0);
+  m.def("cache_topk_wide_tiled", &cache_topk_wide_tiled,
+        "cache_topk_wide's arguments and result from one pass over the index for "
+        "any n_q <= 256: queries are staged in LDS in K chunks, so the pass size "
+        "does not depend on dim.",
+        py::arg("index"), py::arg("q"), py::arg("row_scope") = py::none(),
+        py::arg("row_expiry") = py::none(), py::arg("q_scope") = py::none(),
+        py::arg("now") = 0);
+  m.def("cache_wide_queries_per_pass", &cache_wide_queries_per_pass,
+        "queries one index pass of cache_topk_wide holds", py::arg("dim"), py::arg("fp8"),
+        py::arg("scoped"));
   m.def("mxfp4_quantize_rows", &mxfp4_quantize_rows,
         "bf16 [n, dim] -> (packed e2m1 nibbles u8 [n, dim/2], E8M0 scale u8 "
         "[n, dim/32], inv_norm f32 [n]), dim a multiple of 128 in 128..2048; the "

@@ -23,6 +23,7 @@ HIP_HEADERS = [
     "csrc/cache_kernels.cuh",
     "csrc/cache_kbest_kernels.cuh",
     "csrc/cache_wide_kernels.cuh",
+    "csrc/cache_wide_tiled_kernels.cuh",
     "csrc/mxfp4_kernels.cuh",
     "csrc/mxfp4_wide_kernels.cuh",
     "csrc/prefix_kernels.cuh",
