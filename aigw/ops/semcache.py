@@ -162,6 +162,21 @@ class SemanticCache:
         # a row is live while expiry > now(); fractional ends round up
         return int(min(max(math.ceil(self._now_f() + ttl_s), 0.0), NEVER - 1))
 
+    def _filter_tags(self, n: int, scopes: Optional[list[int]]):
+        """(row_scope, row_expiry, q_scope, now) for a lookup of n queries
+        that filters rows, None for one that does not: no ``scopes``, an
+        unscoped cache and no TTL in play. q_scope covers all n queries; a
+        call of at most 256 takes its slice."""
+        if not self._filtering and scopes is None:
+            return None
+        q_scope = torch.tensor(
+            list(scopes) if scopes is not None else [0] * n,
+            dtype=torch.int64, device=self.device,
+        )
+        if q_scope.shape[0] != n:
+            raise ValueError("scopes must hold one id per query")
+        return self.row_scope[: self.size], self.row_expiry[: self.size], q_scope, self.now()
+
     def lookup(
         self, queries: torch.Tensor, scopes: Optional[list[int]] = None
     ) -> list[Optional[tuple[int, float]]]:
@@ -173,18 +188,10 @@ class SemanticCache:
         if self.size == 0:
             return [None] * queries.shape[0]
         view = self.index[: self.size]
-        filtering = self._filtering or scopes is not None
+        filter_tags = self._filter_tags(queries.shape[0], scopes)
+        filtering = filter_tags is not None
         if filtering:
-            n = queries.shape[0]
-            q_scope = torch.tensor(
-                list(scopes) if scopes is not None else [0] * n,
-                dtype=torch.int64, device=self.device,
-            )
-            if q_scope.shape[0] != n:
-                raise ValueError("scopes must hold one id per query")
-            row_scope = self.row_scope[: self.size]
-            row_expiry = self.row_expiry[: self.size]
-            now = self.now()
+            row_scope, row_expiry, q_scope, now = filter_tags
         hi, idx = [], []
         for q0 in range(0, queries.shape[0], 256):  # kernel cap: 256 q/call
             qs = queries[q0 : q0 + 256].to(self.query_dtype).contiguous()
@@ -275,21 +282,15 @@ class SemanticCache:
         if self.size == 0:
             return [[] for _ in range(n)]
         view = self.index[: self.size]
-        tags = ()
-        if self._filtering or scopes is not None:
-            q_scope = torch.tensor(
-                list(scopes) if scopes is not None else [0] * n,
-                dtype=torch.int64, device=self.device,
-            )
-            if q_scope.shape[0] != n:
-                raise ValueError("scopes must hold one id per query")
-            tags = (self.row_scope[: self.size], self.row_expiry[: self.size])
-            now = self.now()
+        filter_tags = self._filter_tags(n, scopes)
+        if filter_tags is not None:
+            row_scope, row_expiry, q_scope, now = filter_tags
         out: list[list[tuple[int, float]]] = []
         for q0 in range(0, n, 256):  # kernel cap: 256 q/call
             qs = queries[q0 : q0 + 256].to(self.query_dtype).contiguous()
-            if tags:
-                h, i = self.hip.cache_topk_k(view, qs, k, *tags, q_scope[q0 : q0 + 256], now)
+            if filter_tags is not None:
+                h, i = self.hip.cache_topk_k(view, qs, k, row_scope, row_expiry,
+                                             q_scope[q0 : q0 + 256], now)
             else:
                 h, i = self.hip.cache_topk_k(view, qs, k)
             for hs, rows in zip(h.cpu().tolist(), i.cpu().tolist()):

@@ -514,11 +514,11 @@ class GpuAdmissionDirect {
         constexpr size_t L8 = 128 * (12 * 32 + 16) + 128 * 8;
         (void)hipFuncSetAttribute(
             reinterpret_cast<const void*>(
-                &cache_topk_fp8_lds_kernel_t<12, ROWTILES>),
+                &cache_topk_lds_kernel_t<CacheElemFp8, 12, ROWTILES>),
             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         for (int q0 = 0; q0 < n_req; q0 += 128) {
           int kq = (n_req - q0) < 128 ? (n_req - q0) : 128;
-          hipLaunchKernelGGL((cache_topk_fp8_lds_kernel_t<12, ROWTILES>),
+          hipLaunchKernelGGL((cache_topk_lds_kernel_t<CacheElemFp8, 12, ROWTILES>),
                              dim3((unsigned)blocks), dim3(256), L8, st,
                              (const uint8_t*)d_index_, rows_now,
                              b.d_q8 + (size_t)q0 * dim, kq, dim, b.d_best + q0);
@@ -526,11 +526,11 @@ class GpuAdmissionDirect {
       } else {
         constexpr size_t L = 128 * (12 * 32 + 8) * sizeof(bf16) + 128 * 8;
         (void)hipFuncSetAttribute(
-            reinterpret_cast<const void*>(&cache_topk_lds_kernel_t<12, ROWTILES>),
+            reinterpret_cast<const void*>(&cache_topk_lds_kernel_t<CacheElemBf16, 12, ROWTILES>),
             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         for (int q0 = 0; q0 < n_req; q0 += 128) {
           int kq = (n_req - q0) < 128 ? (n_req - q0) : 128;
-          hipLaunchKernelGGL((cache_topk_lds_kernel_t<12, ROWTILES>),
+          hipLaunchKernelGGL((cache_topk_lds_kernel_t<CacheElemBf16, 12, ROWTILES>),
                              dim3((unsigned)blocks), dim3(256), L, st,
                              (const bf16*)d_index_, rows_now,
                              b.d_q + (size_t)q0 * dim, kq, dim, b.d_best + q0);

@@ -28,6 +28,7 @@
 #include <ATen/hip/HIPContext.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #define AIGW_CHECK(cond, msg) TORCH_CHECK(cond, msg)
 
@@ -90,6 +91,172 @@ static inline hipStream_t current_stream() {
 static void check_cuda(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+}
+
+// ---- semantic-cache lookups: what every cache_topk* entry point shares ----
+// An entry point reads: checks (check_cache_dense or check_cache_mxfp4, then
+// cache_tags), launch, epilogue (cache_lookup). `op` names it in the messages.
+
+using OptTensor = c10::optional<at::Tensor>;
+
+constexpr int kCacheRowTiles = 16;  // 16-row tiles per wave of the narrow kernels
+
+struct CacheShape {
+  long long n_rows;
+  int n_q, dim;
+  bool fp8;  // dense index of float8_e4m3fn rows, not bf16
+};
+
+// The row filter of a call; without tags null pointers and now = 0.
+struct CacheTags {
+  bool scoped = false;
+  const long long* row_scope = nullptr;
+  const int* row_expiry = nullptr;
+  const long long* q_scope = nullptr;
+  int now = 0;
+};
+
+static CacheTags cache_tags(const char* op, const at::Tensor& index, const CacheShape& s,
+                            const OptTensor& row_scope, const OptTensor& row_expiry,
+                            const OptTensor& q_scope, int64_t now) {
+  CacheTags t;
+  t.scoped = row_scope.has_value();
+  TORCH_CHECK(row_expiry.has_value() == t.scoped && q_scope.has_value() == t.scoped, op,
+              ": row_scope, row_expiry and q_scope are given together or not at all");
+  if (!t.scoped) return t;
+  check_cuda(*row_scope, "row_scope");
+  check_cuda(*row_expiry, "row_expiry");
+  check_cuda(*q_scope, "q_scope");
+  TORCH_CHECK(row_scope->scalar_type() == at::kLong && row_scope->dim() == 1 &&
+                  row_scope->size(0) == s.n_rows,
+              op, ": ", "row_scope must be int64[n_rows]");
+  TORCH_CHECK(row_expiry->scalar_type() == at::kInt && row_expiry->dim() == 1 &&
+                  row_expiry->size(0) == s.n_rows,
+              op, ": row_expiry must be int32[n_rows]");
+  TORCH_CHECK(q_scope->scalar_type() == at::kLong && q_scope->dim() == 1 &&
+                  q_scope->size(0) == s.n_q,
+              op, ": q_scope must be int64[n_q]");
+  TORCH_CHECK(row_scope->device() == index.device() &&
+                  row_expiry->device() == index.device() &&
+                  q_scope->device() == index.device(),
+              op, ": all tensors must be on one device");
+  // the kernels read a lane's 4 row tags as 16-byte vectors
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(row_scope->data_ptr()) % 32 == 0 &&
+                  reinterpret_cast<uintptr_t>(row_expiry->data_ptr()) % 16 == 0,
+              op, ": row_scope/row_expiry must start 32/16-byte aligned (row 4k of the "
+              "allocation)");
+  TORCH_CHECK(now >= INT32_MIN && now <= INT32_MAX, op, ": now must fit int32");
+  t.row_scope = reinterpret_cast<const long long*>(row_scope->data_ptr<int64_t>());
+  t.row_expiry = row_expiry->data_ptr<int32_t>();
+  t.q_scope = reinterpret_cast<const long long*>(q_scope->data_ptr<int64_t>());
+  t.now = (int)now;
+  return t;
+}
+
+// bf16 or fp8 index [n_rows, dim] against q [n_q <= 256, dim] of the same
+// dtype; dim a multiple of dim_multiple in dim_min..dim_max. align16: the
+// kernel reads rows and queries as 16-byte vectors.
+static CacheShape check_cache_dense(const char* op, const at::Tensor& index,
+                                    const at::Tensor& q, int dim_multiple, int dim_min,
+                                    int dim_max, bool align16) {
+  check_cuda(index, "index");
+  check_cuda(q, "q");
+  bool fp8 = index.scalar_type() == at::kFloat8_e4m3fn;
+  TORCH_CHECK(index.scalar_type() == q.scalar_type(), op, ": index/q dtype mismatch");
+  TORCH_CHECK(fp8 || index.scalar_type() == at::kBFloat16, op,
+              ": bf16 or float8_e4m3fn required");
+  TORCH_CHECK(index.dim() == 2 && q.dim() == 2, op, ": index and q must be 2-D");
+  long long dim = q.size(1);
+  TORCH_CHECK(index.size(1) == dim, op, ": index/q dim mismatch");
+  TORCH_CHECK(dim % dim_multiple == 0 && dim >= dim_min && dim <= dim_max, op,
+              ": dim must be a multiple of ", dim_multiple, " in ", dim_min, "..", dim_max,
+              ", got ", dim);
+  TORCH_CHECK(q.size(0) <= 256, op, ": at most 256 queries per call");
+  TORCH_CHECK(q.device() == index.device(), op, ": all tensors must be on one device");
+  TORCH_CHECK(!align16 || (reinterpret_cast<uintptr_t>(index.data_ptr()) % 16 == 0 &&
+                           reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0),
+              op, ": index and q must start 16-byte aligned");
+  return {index.size(0), (int)q.size(0), (int)dim, fp8};
+}
+
+// MXFP4 index (mxfp4_quantize_rows output) against float8_e4m3fn q
+// [n_q <= 256, dim]; dim a multiple of 128 in dim_min..dim_max.
+static CacheShape check_cache_mxfp4(const char* op, const at::Tensor& packed,
+                                    const at::Tensor& scale, const at::Tensor& inv_norm,
+                                    const at::Tensor& q, int dim_min, int dim_max) {
+  check_cuda(packed, "packed");
+  check_cuda(scale, "scale");
+  check_cuda(inv_norm, "inv_norm");
+  check_cuda(q, "q");
+  TORCH_CHECK(q.scalar_type() == at::kFloat8_e4m3fn && q.dim() == 2, op,
+              ": q must be float8_e4m3fn [n_q, dim]");
+  long long dim = q.size(1);
+  TORCH_CHECK(dim % 128 == 0 && dim >= dim_min && dim <= dim_max, op,
+              ": dim must be a multiple of 128 in ", dim_min, "..", dim_max, ", got ", dim);
+  TORCH_CHECK(packed.scalar_type() == at::kByte && packed.dim() == 2 &&
+                  packed.size(1) == dim / 2,
+              op, ": packed must be uint8 [n_rows, dim/2]");
+  long long n_rows = packed.size(0);
+  TORCH_CHECK(scale.scalar_type() == at::kByte && scale.dim() == 2 &&
+                  scale.size(0) == n_rows && scale.size(1) == dim / 32,
+              op, ": scale must be uint8 [n_rows, dim/32]");
+  TORCH_CHECK(inv_norm.scalar_type() == at::kFloat && inv_norm.dim() == 1 &&
+                  inv_norm.size(0) == n_rows,
+              op, ": inv_norm must be float32 [n_rows]");
+  TORCH_CHECK(q.size(0) <= 256, op, ": at most 256 queries per call");
+  TORCH_CHECK(scale.device() == packed.device() && inv_norm.device() == packed.device() &&
+                  q.device() == packed.device(),
+              op, ": all tensors must be on one device");
+  // 16-byte row and query fragments, a dword of scale bytes per k-step,
+  // 16 bytes of inv_norm per 4 result rows
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(packed.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(scale.data_ptr()) % 4 == 0 &&
+                  reinterpret_cast<uintptr_t>(inv_norm.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              op, ": packed/inv_norm/q must start 16-byte and scale 4-byte aligned");
+  return {n_rows, (int)q.size(0), (int)dim, false};
+}
+
+// Allocates `best` (`shape` keys of orderable score << 32 | row, zeroed), has
+// `launch` fill it unless the call is empty, and unpacks it to (hi int64,
+// idx int32): score = orderable^-1(hi), row = idx. no_row_is_zero: a key the
+// kernels left 0 means no row may answer, idx -1 / hi 0.
+template <class Launch>
+static std::vector<at::Tensor> cache_lookup(const CacheShape& s, const at::Tensor& q,
+                                            at::IntArrayRef shape, bool no_row_is_zero,
+                                            Launch&& launch) {
+  auto best = at::zeros(shape, at::TensorOptions().dtype(at::kLong).device(q.device()));
+  if (s.n_q == 0 || s.n_rows == 0)
+    return {best, at::full(shape, -1, best.options().dtype(at::kInt))};
+  launch(best);
+  auto hi = best.bitwise_right_shift(32).to(at::kLong);
+  auto idx = best.bitwise_and(0xFFFFFFFFLL);
+  if (no_row_is_zero) idx = at::where(best == 0, -1, idx);
+  return {hi, idx.to(at::kInt)};
+}
+
+// dim -> compile-time KSTEPS, the row's k-steps of 32 elements: 4/8/12/16 for
+// dim 128/256/384/512, handed to f as a std::integral_constant. An MXFP4
+// kernel counts its k-steps of 128 elements: KSTEPS / 4.
+template <class F>
+static void dispatch_ksteps(const char* op, int dim, F&& f) {
+  switch (dim >> 5) {
+    case 12: f(std::integral_constant<int, 12>{}); break;  // 384 (bge-small): the hot path
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    case 16: f(std::integral_constant<int, 16>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    default:
+      TORCH_CHECK(false, op, ": unsupported dim ", dim, " (supported: 128/256/384/512)");
+  }
+}
+
+// (fp8, scoped) -> f(element traits, std::bool_constant<SCOPED>)
+template <class F>
+static auto dispatch_elem_scoped(bool fp8, bool scoped, F&& f) {
+  if (fp8 && scoped) return f(CacheElemFp8{}, std::true_type{});
+  if (fp8) return f(CacheElemFp8{}, std::false_type{});
+  if (scoped) return f(CacheElemBf16{}, std::true_type{});
+  return f(CacheElemBf16{}, std::false_type{});
 }
 
 // Returns (seg_start, seg_req, n_segs is seg_start.numel())
@@ -319,210 +486,70 @@ at::Tensor l2norm_rows(at::Tensor x) {
   return out;
 }
 
-std::vector<at::Tensor> cache_topk(at::Tensor index, at::Tensor q) {
-  check_cuda(index, "index");
-  check_cuda(q, "q");
-  bool fp8 = index.scalar_type() == at::kFloat8_e4m3fn;
-  TORCH_CHECK(index.scalar_type() == q.scalar_type(), "index/q dtype mismatch");
-  TORCH_CHECK(fp8 || index.scalar_type() == at::kBFloat16,
-              "bf16 or float8_e4m3fn required");
-  long long n_rows = index.size(0);
-  int n_q = (int)q.size(0), dim = (int)q.size(1);
-  TORCH_CHECK(index.size(1) == dim, "dim mismatch");
-  TORCH_CHECK(dim % 32 == 0 && dim <= 512, "dim must be a multiple of 32, <= 512");
-  auto best = at::zeros({n_q}, at::TensorOptions()
-                                   .dtype(at::kLong)
-                                   .device(q.device()));
-  TORCH_CHECK(n_q <= 256, "cache_topk: at most 256 queries per call");
-  constexpr int ROWTILES = 16;
-  long long blocks = (n_rows + 64 * ROWTILES - 1) / (64 * ROWTILES);
+// The arg-max kernels of cache_kernels.cuh, unfiltered or filtered: passes of
+// <= 128 queries (the query block lives in LDS), each one launch that streams
+// the whole index — two passes for 256 queries still beat a register-tile
+// kernel's latency stalls by a wide margin.
+template <class E, bool SCOPED>
+static void launch_cache_topk(const char* op, const CacheShape& s, const at::Tensor& index,
+                              const at::Tensor& q, const CacheTags& t, at::Tensor& best) {
+  using elem = typename E::elem;
+  long long blocks = (s.n_rows + 64 * kCacheRowTiles - 1) / (64 * kCacheRowTiles);
+  auto* ip = reinterpret_cast<const elem*>(index.data_ptr());
+  auto* q_base = reinterpret_cast<const elem*>(q.data_ptr());
   auto* best_p = reinterpret_cast<unsigned long long*>(best.data_ptr<int64_t>());
-  if (fp8) {
-    auto* ip = reinterpret_cast<const uint8_t*>(index.data_ptr());
-    auto* q_base = reinterpret_cast<const uint8_t*>(q.data_ptr());
-    auto launch_fp8 = [&](auto kernel, int kq, const uint8_t* qp,
-                          unsigned long long* bp, size_t lds_bytes) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024);
-      hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), lds_bytes,
-                         current_stream(), ip, n_rows, qp, kq, dim, bp);
-    };
-    for (int q0 = 0; q0 < n_q; q0 += 128) {
-      int kq = std::min(128, n_q - q0);
-      const uint8_t* qp = q_base + (long long)q0 * dim;
-      unsigned long long* bp = best_p + q0;
-      switch (dim >> 5) {
-        case 12: {
-          constexpr size_t L = 128 * (12 * 32 + 16) + 128 * 8;
-          launch_fp8(&cache_topk_fp8_lds_kernel_t<12, ROWTILES>, kq, qp, bp, L);
-          break;
-        }
-        case 8: {
-          constexpr size_t L = 128 * (8 * 32 + 16) + 128 * 8;
-          launch_fp8(&cache_topk_fp8_lds_kernel_t<8, ROWTILES>, kq, qp, bp, L);
-          break;
-        }
-        case 16: {
-          constexpr size_t L = 128 * (16 * 32 + 16) + 128 * 8;
-          launch_fp8(&cache_topk_fp8_lds_kernel_t<16, ROWTILES>, kq, qp, bp, L);
-          break;
-        }
-        case 4: {
-          constexpr size_t L = 128 * (4 * 32 + 16) + 128 * 8;
-          launch_fp8(&cache_topk_fp8_lds_kernel_t<4, ROWTILES>, kq, qp, bp, L);
-          break;
-        }
-        default:
-          TORCH_CHECK(false, "cache_topk fp8: unsupported dim ", dim);
-      }
-    }
-    auto hi = best.bitwise_right_shift(32).to(at::kLong);
-    auto idx = best.bitwise_and(0xFFFFFFFFLL).to(at::kInt);
-    return {hi, idx};
-  }
-  auto* index_p = reinterpret_cast<bf16*>(index.data_ptr<at::BFloat16>());
-  auto* q_p = reinterpret_cast<bf16*>(q.data_ptr<at::BFloat16>());
-  // bf16 path: LDS-staged kernel, <=128 queries per pass (the query block
-  // lives in LDS; see cache_topk_lds_kernel_t). The index streams once
-  // per pass — two passes for 256 queries still beat the register-tile
-  // kernel's latency stalls by a wide margin.
-  auto launch_lds = [&](auto kernel, int kq, const bf16* qp, unsigned long long* bp,
-                        size_t lds_bytes) {
+  // query block + blk_best (+ q_scope stage)
+  size_t lds_bytes = 128 * (size_t)(s.dim + E::kPad) * sizeof(elem) + 128 * 8 +
+                     (SCOPED ? 128 * 8 : 0);
+  auto launch = [&](auto kernel, int q0, auto... tags) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), lds_bytes,
-                       current_stream(), index_p, n_rows, qp, kq, dim, bp);
+                       current_stream(), ip, s.n_rows, q_base + (long long)q0 * s.dim,
+                       std::min(128, s.n_q - q0), s.dim, best_p + q0, tags...);
   };
-  for (int q0 = 0; q0 < n_q; q0 += 128) {
-    int kq = std::min(128, n_q - q0);
-    const bf16* qp = q_p + (long long)q0 * dim;
-    unsigned long long* bp = best_p + q0;
-    switch (dim >> 5) {
-      case 12: {  // dim = 384 (bge-small) — the hot path
-        constexpr size_t L = 128 * (12 * 32 + 8) * sizeof(bf16) + 128 * 8;
-        launch_lds(&cache_topk_lds_kernel_t<12, ROWTILES>, kq, qp, bp, L);
-        break;
-      }
-      case 8: {  // dim = 256
-        constexpr size_t L = 128 * (8 * 32 + 8) * sizeof(bf16) + 128 * 8;
-        launch_lds(&cache_topk_lds_kernel_t<8, ROWTILES>, kq, qp, bp, L);
-        break;
-      }
-      case 16: {  // dim = 512
-        constexpr size_t L = 128 * (16 * 32 + 8) * sizeof(bf16) + 128 * 8;
-        launch_lds(&cache_topk_lds_kernel_t<16, ROWTILES>, kq, qp, bp, L);
-        break;
-      }
-      case 4: {  // dim = 128
-        constexpr size_t L = 128 * (4 * 32 + 8) * sizeof(bf16) + 128 * 8;
-        launch_lds(&cache_topk_lds_kernel_t<4, ROWTILES>, kq, qp, bp, L);
-        break;
-      }
-      default:
-        TORCH_CHECK(false, "cache_topk: unsupported dim ", dim,
-                    " (supported: 128/256/384/512)");
+  dispatch_ksteps(op, s.dim, [&](auto ks) {
+    constexpr int KSTEPS = decltype(ks)::value;
+    for (int q0 = 0; q0 < s.n_q; q0 += 128) {
+      if constexpr (SCOPED)
+        launch(&cache_topk_scoped_kernel_t<E, KSTEPS, kCacheRowTiles>, q0, t.row_scope,
+               t.row_expiry, t.q_scope + q0, t.now);
+      else
+        launch(&cache_topk_lds_kernel_t<E, KSTEPS, kCacheRowTiles>, q0);
     }
-  }
-  // unpack: score = orderable^-1(hi32), idx = lo32
-  auto hi = best.bitwise_right_shift(32).to(at::kLong);
-  auto idx = best.bitwise_and(0xFFFFFFFFLL).to(at::kInt);
-  return {hi, idx};
+  });
+}
+
+// (hi, idx) of the best row per query, 128..512 elements per row: the
+// unfiltered arg-max kernel without tags, the filtered one with them.
+static std::vector<at::Tensor> cache_topk_narrow(const char* op, const at::Tensor& index,
+                                                 const at::Tensor& q, const OptTensor& row_scope,
+                                                 const OptTensor& row_expiry,
+                                                 const OptTensor& q_scope, int64_t now) {
+  // of these widths dispatch_ksteps serves 128/256/384/512 and refuses the rest
+  CacheShape s = check_cache_dense(op, index, q, 32, 0, 512, false);
+  CacheTags t = cache_tags(op, index, s, row_scope, row_expiry, q_scope, now);
+  // unfiltered, every query gets a row and best is never 0 (pack_score of a
+  // real score is not), so the sentinel mapping's two launches are skipped
+  return cache_lookup(s, q, {s.n_q}, t.scoped, [&](at::Tensor& best) {
+    dispatch_elem_scoped(s.fp8, t.scoped, [&](auto e, auto scoped) {
+      launch_cache_topk<decltype(e), decltype(scoped)::value>(op, s, index, q, t, best);
+    });
+  });
+}
+
+std::vector<at::Tensor> cache_topk(at::Tensor index, at::Tensor q) {
+  return cache_topk_narrow("cache_topk", index, q, c10::nullopt, c10::nullopt, c10::nullopt, 0);
 }
 
 // cache_topk with the per-row (scope, expiry) filter of
 // cache_topk_scoped_kernel_t: a query sees row r only if
 // row_expiry[r] > now and (q_scope == 0 or row_scope[r] == q_scope).
 // idx is -1 and hi is 0 for a query that no row may answer.
-template <class E>
-static void launch_cache_topk_scoped(const at::Tensor& index, const at::Tensor& q,
-                                     const at::Tensor& row_scope,
-                                     const at::Tensor& row_expiry,
-                                     const at::Tensor& q_scope, int now,
-                                     at::Tensor& best) {
-  using elem = typename E::elem;
-  constexpr int ROWTILES = 16;
-  long long n_rows = index.size(0);
-  int n_q = (int)q.size(0), dim = (int)q.size(1);
-  long long blocks = (n_rows + 64 * ROWTILES - 1) / (64 * ROWTILES);
-  auto* ip = reinterpret_cast<const elem*>(index.data_ptr());
-  auto* q_base = reinterpret_cast<const elem*>(q.data_ptr());
-  auto* best_p = reinterpret_cast<unsigned long long*>(best.data_ptr<int64_t>());
-  auto* rs = reinterpret_cast<const long long*>(row_scope.data_ptr<int64_t>());
-  auto* re = row_expiry.data_ptr<int32_t>();
-  auto* qsc = reinterpret_cast<const long long*>(q_scope.data_ptr<int64_t>());
-  // query block + blk_best + q_scope stage
-  size_t lds_bytes = 128 * (size_t)(dim + E::kPad) * sizeof(elem) + 128 * 8 + 128 * 8;
-  auto launch = [&](auto kernel, int q0) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), lds_bytes,
-                       current_stream(), ip, n_rows, q_base + (long long)q0 * dim,
-                       std::min(128, n_q - q0), dim, best_p + q0, rs, re, qsc + q0, now);
-  };
-  for (int q0 = 0; q0 < n_q; q0 += 128) {
-    switch (dim >> 5) {
-      case 12: launch(&cache_topk_scoped_kernel_t<E, 12, ROWTILES>, q0); break;
-      case 8: launch(&cache_topk_scoped_kernel_t<E, 8, ROWTILES>, q0); break;
-      case 16: launch(&cache_topk_scoped_kernel_t<E, 16, ROWTILES>, q0); break;
-      case 4: launch(&cache_topk_scoped_kernel_t<E, 4, ROWTILES>, q0); break;
-      default:
-        TORCH_CHECK(false, "cache_topk_scoped: unsupported dim ", dim,
-                    " (supported: 128/256/384/512)");
-    }
-  }
-}
-
 std::vector<at::Tensor> cache_topk_scoped(at::Tensor index, at::Tensor q,
                                           at::Tensor row_scope, at::Tensor row_expiry,
                                           at::Tensor q_scope, int64_t now) {
-  check_cuda(index, "index");
-  check_cuda(q, "q");
-  check_cuda(row_scope, "row_scope");
-  check_cuda(row_expiry, "row_expiry");
-  check_cuda(q_scope, "q_scope");
-  bool fp8 = index.scalar_type() == at::kFloat8_e4m3fn;
-  TORCH_CHECK(index.scalar_type() == q.scalar_type(), "index/q dtype mismatch");
-  TORCH_CHECK(fp8 || index.scalar_type() == at::kBFloat16,
-              "bf16 or float8_e4m3fn required");
-  TORCH_CHECK(index.dim() == 2 && q.dim() == 2, "index and q must be 2-D");
-  long long n_rows = index.size(0);
-  int n_q = (int)q.size(0), dim = (int)q.size(1);
-  TORCH_CHECK(index.size(1) == dim, "dim mismatch");
-  TORCH_CHECK(dim % 32 == 0 && dim <= 512, "dim must be a multiple of 32, <= 512");
-  TORCH_CHECK(n_q <= 256, "cache_topk_scoped: at most 256 queries per call");
-  TORCH_CHECK(row_scope.scalar_type() == at::kLong && row_scope.dim() == 1 &&
-                  row_scope.size(0) == n_rows,
-              "row_scope must be int64[n_rows]");
-  TORCH_CHECK(row_expiry.scalar_type() == at::kInt && row_expiry.dim() == 1 &&
-                  row_expiry.size(0) == n_rows,
-              "row_expiry must be int32[n_rows]");
-  TORCH_CHECK(q_scope.scalar_type() == at::kLong && q_scope.dim() == 1 &&
-                  q_scope.size(0) == n_q,
-              "q_scope must be int64[n_q]");
-  TORCH_CHECK(row_scope.device() == index.device() &&
-                  row_expiry.device() == index.device() &&
-                  q_scope.device() == index.device() && q.device() == index.device(),
-              "cache_topk_scoped: all tensors must be on one device");
-  // the kernel reads a lane's 4 row tags as 16-byte vectors
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(row_scope.data_ptr()) % 32 == 0 &&
-                  reinterpret_cast<uintptr_t>(row_expiry.data_ptr()) % 16 == 0,
-              "row_scope/row_expiry must start 32/16-byte aligned (row 4k of the "
-              "allocation)");
-  TORCH_CHECK(now >= INT32_MIN && now <= INT32_MAX, "now must fit int32");
-  auto best = at::zeros({n_q}, at::TensorOptions().dtype(at::kLong).device(q.device()));
-  if (n_q == 0 || n_rows == 0)
-    return {best, at::full({n_q}, -1, best.options().dtype(at::kInt))};
-  if (fp8)
-    launch_cache_topk_scoped<CacheElemFp8>(index, q, row_scope, row_expiry, q_scope,
-                                           (int)now, best);
-  else
-    launch_cache_topk_scoped<CacheElemBf16>(index, q, row_scope, row_expiry, q_scope,
-                                            (int)now, best);
-  auto hi = best.bitwise_right_shift(32).to(at::kLong);
-  auto idx = at::where(best == 0, -1, best.bitwise_and(0xFFFFFFFFLL)).to(at::kInt);
-  return {hi, idx};
+  return cache_topk_narrow("cache_topk_scoped", index, q, row_scope, row_expiry, q_scope, now);
 }
 
 // The k best eligible rows per query (cache_kbest_kernels.cuh): one scan
@@ -530,50 +557,35 @@ std::vector<at::Tensor> cache_topk_scoped(at::Tensor index, at::Tensor q,
 // ([blocks, n_q, k] keys), one merge launch folds them into `best`
 // ([n_q, k] keys, descending, 0 = no row).
 template <class E, bool SCOPED>
-static void launch_cache_topk_k(const at::Tensor& index, const at::Tensor& q, int k,
-                                const long long* rs, const int* re, const long long* qsc,
-                                int now, at::Tensor& best) {
+static void launch_cache_topk_k(const char* op, const CacheShape& s, const at::Tensor& index,
+                                const at::Tensor& q, int k, const CacheTags& t,
+                                at::Tensor& best) {
   using elem = typename E::elem;
-  constexpr int ROWTILES = 16;
-  long long n_rows = index.size(0);
-  int n_q = (int)q.size(0), dim = (int)q.size(1);
-  long long blocks = (n_rows + 64 * ROWTILES - 1) / (64 * ROWTILES);
-  auto part = at::empty({blocks, n_q, k}, best.options());
+  long long blocks = (s.n_rows + 64 * kCacheRowTiles - 1) / (64 * kCacheRowTiles);
+  auto part = at::empty({blocks, s.n_q, k}, best.options());
   auto* ip = reinterpret_cast<const elem*>(index.data_ptr());
   auto* q_base = reinterpret_cast<const elem*>(q.data_ptr());
   auto* part_p = reinterpret_cast<unsigned long long*>(part.data_ptr<int64_t>());
   auto* best_p = reinterpret_cast<unsigned long long*>(best.data_ptr<int64_t>());
-  auto launch = [&](auto kernel, int qb) {
+  dispatch_ksteps(op, s.dim, [&](auto ks) {
+    constexpr int KSTEPS = decltype(ks)::value;
+    auto kernel = &cache_topk_k_kernel_t<E, KSTEPS, kCacheRowTiles, SCOPED>;
+    const int qb = 16 * kbest_qtiles<E, KSTEPS>();
     // query block + wave lists (+ q_scope stage)
-    size_t lds_bytes = (size_t)qb * (dim + E::kPad) * sizeof(elem) +
+    size_t lds_bytes = (size_t)qb * (s.dim + E::kPad) * sizeof(elem) +
                        (size_t)4 * qb * kbest_list_stride(k) * 8 + (SCOPED ? qb * 8 : 0);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
                               hipFuncAttributeMaxDynamicSharedMemorySize, kKbestLdsLimit);
-    for (int q0 = 0; q0 < n_q; q0 += qb)
+    for (int q0 = 0; q0 < s.n_q; q0 += qb)
       hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), lds_bytes,
-                         current_stream(), ip, n_rows, q_base + (long long)q0 * dim,
-                         std::min(qb, n_q - q0), dim, k, part_p + (long long)q0 * k,
-                         (long long)n_q * k, rs, re, SCOPED ? qsc + q0 : nullptr, now);
-  };
-  switch (dim >> 5) {
-    case 12:
-      launch(&cache_topk_k_kernel_t<E, 12, ROWTILES, SCOPED>, 16 * kbest_qtiles<E, 12>());
-      break;
-    case 8:
-      launch(&cache_topk_k_kernel_t<E, 8, ROWTILES, SCOPED>, 16 * kbest_qtiles<E, 8>());
-      break;
-    case 16:
-      launch(&cache_topk_k_kernel_t<E, 16, ROWTILES, SCOPED>, 16 * kbest_qtiles<E, 16>());
-      break;
-    case 4:
-      launch(&cache_topk_k_kernel_t<E, 4, ROWTILES, SCOPED>, 16 * kbest_qtiles<E, 4>());
-      break;
-    default:
-      TORCH_CHECK(false, "cache_topk_k: unsupported dim ", dim,
-                  " (supported: 128/256/384/512)");
-  }
-  hipLaunchKernelGGL(cache_topk_k_merge_kernel<kKbestMax>, dim3((unsigned)((n_q + 3) / 4)),
-                     dim3(256), 0, current_stream(), part_p, blocks, n_q, k, best_p);
+                         current_stream(), ip, s.n_rows, q_base + (long long)q0 * s.dim,
+                         std::min(qb, s.n_q - q0), s.dim, k, part_p + (long long)q0 * k,
+                         (long long)s.n_q * k, t.row_scope, t.row_expiry,
+                         SCOPED ? t.q_scope + q0 : nullptr, t.now);
+  });
+  hipLaunchKernelGGL(cache_topk_k_merge_kernel<kKbestMax>,
+                     dim3((unsigned)((s.n_q + 3) / 4)), dim3(256), 0, current_stream(), part_p,
+                     blocks, s.n_q, k, best_p);
 }
 
 // (hi int64 [n_q, k], idx int32 [n_q, k]) in cache_topk_scoped's encoding,
@@ -583,101 +595,81 @@ std::vector<at::Tensor> cache_topk_k(at::Tensor index, at::Tensor q, int64_t k,
                                      c10::optional<at::Tensor> row_scope,
                                      c10::optional<at::Tensor> row_expiry,
                                      c10::optional<at::Tensor> q_scope, int64_t now) {
-  check_cuda(index, "index");
-  check_cuda(q, "q");
-  bool scoped = row_scope.has_value();
-  TORCH_CHECK(row_expiry.has_value() == scoped && q_scope.has_value() == scoped,
-              "cache_topk_k: row_scope, row_expiry and q_scope are given together or "
-              "not at all");
-  bool fp8 = index.scalar_type() == at::kFloat8_e4m3fn;
-  TORCH_CHECK(index.scalar_type() == q.scalar_type(), "index/q dtype mismatch");
-  TORCH_CHECK(fp8 || index.scalar_type() == at::kBFloat16,
-              "bf16 or float8_e4m3fn required");
-  TORCH_CHECK(index.dim() == 2 && q.dim() == 2, "index and q must be 2-D");
-  TORCH_CHECK(index.is_contiguous() && q.is_contiguous(),
-              "cache_topk_k: index and q must be contiguous");
-  long long n_rows = index.size(0);
-  int n_q = (int)q.size(0), dim = (int)q.size(1);
-  TORCH_CHECK(index.size(1) == dim, "dim mismatch");
-  TORCH_CHECK(dim % 32 == 0 && dim <= 512, "dim must be a multiple of 32, <= 512");
-  TORCH_CHECK(n_q <= 256, "cache_topk_k: at most 256 queries per call");
-  TORCH_CHECK(k >= 1 && k <= kKbestMax, "cache_topk_k: k must be in [1, ", kKbestMax,
-              "], got ", k);
-  TORCH_CHECK(q.device() == index.device(),
-              "cache_topk_k: all tensors must be on one device");
-  const long long *rs = nullptr, *qsc = nullptr;
-  const int* re = nullptr;
-  if (scoped) {
-    check_cuda(*row_scope, "row_scope");
-    check_cuda(*row_expiry, "row_expiry");
-    check_cuda(*q_scope, "q_scope");
-    TORCH_CHECK(row_scope->scalar_type() == at::kLong && row_scope->dim() == 1 &&
-                    row_scope->size(0) == n_rows,
-                "row_scope must be int64[n_rows]");
-    TORCH_CHECK(row_expiry->scalar_type() == at::kInt && row_expiry->dim() == 1 &&
-                    row_expiry->size(0) == n_rows,
-                "row_expiry must be int32[n_rows]");
-    TORCH_CHECK(q_scope->scalar_type() == at::kLong && q_scope->dim() == 1 &&
-                    q_scope->size(0) == n_q,
-                "q_scope must be int64[n_q]");
-    TORCH_CHECK(row_scope->device() == index.device() &&
-                    row_expiry->device() == index.device() &&
-                    q_scope->device() == index.device(),
-                "cache_topk_k: all tensors must be on one device");
-    TORCH_CHECK(row_scope->is_contiguous() && row_expiry->is_contiguous() &&
-                    q_scope->is_contiguous(),
-                "cache_topk_k: tag tensors must be contiguous");
-    // the kernel reads a lane's 4 row tags as 16-byte vectors
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(row_scope->data_ptr()) % 32 == 0 &&
-                    reinterpret_cast<uintptr_t>(row_expiry->data_ptr()) % 16 == 0,
-                "row_scope/row_expiry must start 32/16-byte aligned (row 4k of the "
-                "allocation)");
-    TORCH_CHECK(now >= INT32_MIN && now <= INT32_MAX, "now must fit int32");
-    rs = reinterpret_cast<const long long*>(row_scope->data_ptr<int64_t>());
-    re = row_expiry->data_ptr<int32_t>();
-    qsc = reinterpret_cast<const long long*>(q_scope->data_ptr<int64_t>());
-  }
-  auto best = at::zeros({n_q, k}, at::TensorOptions().dtype(at::kLong).device(q.device()));
-  if (n_q == 0 || n_rows == 0)
-    return {best, at::full({n_q, k}, -1, best.options().dtype(at::kInt))};
-  int kk = (int)k, nw = scoped ? (int)now : 0;
-  if (fp8 && scoped)
-    launch_cache_topk_k<CacheElemFp8, true>(index, q, kk, rs, re, qsc, nw, best);
-  else if (fp8)
-    launch_cache_topk_k<CacheElemFp8, false>(index, q, kk, rs, re, qsc, nw, best);
-  else if (scoped)
-    launch_cache_topk_k<CacheElemBf16, true>(index, q, kk, rs, re, qsc, nw, best);
-  else
-    launch_cache_topk_k<CacheElemBf16, false>(index, q, kk, rs, re, qsc, nw, best);
-  auto hi = best.bitwise_right_shift(32).to(at::kLong);
-  auto idx = at::where(best == 0, -1, best.bitwise_and(0xFFFFFFFFLL)).to(at::kInt);
-  return {hi, idx};
+  const char* op = "cache_topk_k";
+  CacheShape s = check_cache_dense(op, index, q, 32, 0, 512, false);
+  TORCH_CHECK(k >= 1 && k <= kKbestMax, op, ": k must be in [1, ", kKbestMax, "], got ", k);
+  CacheTags t = cache_tags(op, index, s, row_scope, row_expiry, q_scope, now);
+  return cache_lookup(s, q, {s.n_q, k}, true, [&](at::Tensor& best) {
+    dispatch_elem_scoped(s.fp8, t.scoped, [&](auto e, auto scoped) {
+      launch_cache_topk_k<decltype(e), decltype(scoped)::value>(op, s, index, q, (int)k, t,
+                                                               best);
+    });
+  });
 }
 
 // Wide rows (cache_wide_kernels.cuh): passes of wide_queries_per_pass
 // queries, each one launch that streams the whole index.
 template <class E, bool SCOPED>
-static void launch_cache_topk_wide(const at::Tensor& index, const at::Tensor& q,
-                                   const long long* rs, const int* re, const long long* qsc,
-                                   int now, at::Tensor& best) {
+static void launch_cache_topk_wide(const CacheShape& s, const at::Tensor& index,
+                                   const at::Tensor& q, const CacheTags& t, at::Tensor& best) {
   using elem = typename E::elem;
-  long long n_rows = index.size(0);
-  int n_q = (int)q.size(0), dim = (int)q.size(1);
-  long long blocks = (n_rows + 64 * kWideRowTiles - 1) / (64 * kWideRowTiles);
+  long long blocks = (s.n_rows + 64 * kWideRowTiles - 1) / (64 * kWideRowTiles);
   auto* ip = reinterpret_cast<const elem*>(index.data_ptr());
   auto* q_base = reinterpret_cast<const elem*>(q.data_ptr());
   auto* best_p = reinterpret_cast<unsigned long long*>(best.data_ptr<int64_t>());
   auto kernel = &cache_topk_wide_kernel_t<E, SCOPED>;
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
                             hipFuncAttributeMaxDynamicSharedMemorySize, kWideLdsLimit);
-  const int qb = wide_queries_per_pass<E, SCOPED>(dim);
-  for (int q0 = 0; q0 < n_q; q0 += qb) {
-    int kq = std::min(qb, n_q - q0);
-    size_t lds_bytes = wide_lds_bytes<E, SCOPED>(dim, kq);
+  const int qb = wide_queries_per_pass<E, SCOPED>(s.dim);
+  for (int q0 = 0; q0 < s.n_q; q0 += qb) {
+    int kq = std::min(qb, s.n_q - q0);
+    size_t lds_bytes = wide_lds_bytes<E, SCOPED>(s.dim, kq);
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), lds_bytes,
-                       current_stream(), ip, n_rows, q_base + (long long)q0 * dim, kq, dim,
-                       best_p + q0, rs, re, SCOPED ? qsc + q0 : nullptr, now);
+                       current_stream(), ip, s.n_rows, q_base + (long long)q0 * s.dim, kq,
+                       s.dim, best_p + q0, t.row_scope, t.row_expiry,
+                       SCOPED ? t.q_scope + q0 : nullptr, t.now);
   }
+}
+
+// Wide rows, tiled (cache_wide_tiled_kernels.cuh): one launch for up to 256
+// queries, dynamic LDS sized by the call's query tiles.
+template <class E, bool SCOPED>
+static void launch_cache_topk_wide_tiled(const CacheShape& s, const at::Tensor& index,
+                                         const at::Tensor& q, const CacheTags& t,
+                                         at::Tensor& best) {
+  using elem = typename E::elem;
+  long long blocks = (s.n_rows + kWideTiledBlockRows - 1) / kWideTiledBlockRows;
+  auto kernel = &cache_topk_wide_tiled_kernel_t<E, SCOPED>;
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, kWideLdsLimit);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256),
+                     (size_t)wide_tiled_lds_bytes<SCOPED>(s.n_q), current_stream(),
+                     reinterpret_cast<const elem*>(index.data_ptr()), s.n_rows,
+                     reinterpret_cast<const elem*>(q.data_ptr()), s.n_q, s.dim,
+                     reinterpret_cast<unsigned long long*>(best.data_ptr<int64_t>()),
+                     t.row_scope, t.row_expiry, t.q_scope, t.now);
+}
+
+// Checks and (hi, idx) of both wide-row entry points; `tiled` picks the launch.
+static std::vector<at::Tensor> cache_topk_wide_rows(const char* op, bool tiled,
+                                                    const at::Tensor& index,
+                                                    const at::Tensor& q,
+                                                    const OptTensor& row_scope,
+                                                    const OptTensor& row_expiry,
+                                                    const OptTensor& q_scope, int64_t now) {
+  // rows and queries are read as 16-byte vectors
+  CacheShape s = check_cache_dense(op, index, q, kWideChunk, 640, kWideMaxDim, true);
+  CacheTags t = cache_tags(op, index, s, row_scope, row_expiry, q_scope, now);
+  return cache_lookup(s, q, {s.n_q}, true, [&](at::Tensor& best) {
+    dispatch_elem_scoped(s.fp8, t.scoped, [&](auto e, auto scoped) {
+      using E = decltype(e);
+      constexpr bool SCOPED = decltype(scoped)::value;
+      if (tiled)
+        launch_cache_topk_wide_tiled<E, SCOPED>(s, index, q, t, best);
+      else
+        launch_cache_topk_wide<E, SCOPED>(s, index, q, t, best);
+    });
+  });
 }
 
 // cache_topk_scoped's (hi, idx) for rows of 640..2048 elements; without the
@@ -686,101 +678,8 @@ std::vector<at::Tensor> cache_topk_wide(at::Tensor index, at::Tensor q,
                                         c10::optional<at::Tensor> row_scope,
                                         c10::optional<at::Tensor> row_expiry,
                                         c10::optional<at::Tensor> q_scope, int64_t now) {
-  check_cuda(index, "index");
-  check_cuda(q, "q");
-  bool scoped = row_scope.has_value();
-  TORCH_CHECK(row_expiry.has_value() == scoped && q_scope.has_value() == scoped,
-              "cache_topk_wide: row_scope, row_expiry and q_scope are given together or "
-              "not at all");
-  bool fp8 = index.scalar_type() == at::kFloat8_e4m3fn;
-  TORCH_CHECK(index.scalar_type() == q.scalar_type(), "index/q dtype mismatch");
-  TORCH_CHECK(fp8 || index.scalar_type() == at::kBFloat16,
-              "bf16 or float8_e4m3fn required");
-  TORCH_CHECK(index.dim() == 2 && q.dim() == 2, "index and q must be 2-D");
-  TORCH_CHECK(index.is_contiguous() && q.is_contiguous(),
-              "cache_topk_wide: index and q must be contiguous");
-  long long n_rows = index.size(0);
-  int n_q = (int)q.size(0);
-  long long dim = q.size(1);
-  TORCH_CHECK(index.size(1) == dim, "dim mismatch");
-  TORCH_CHECK(dim % kWideChunk == 0 && dim > 512 && dim <= kWideMaxDim,
-              "cache_topk_wide: dim must be a multiple of 128 in 640..2048, got ", dim,
-              " (128..512: cache_topk, cache_topk_scoped)");
-  TORCH_CHECK(n_q <= 256, "cache_topk_wide: at most 256 queries per call");
-  TORCH_CHECK(q.device() == index.device(),
-              "cache_topk_wide: all tensors must be on one device");
-  // rows and queries are read as 16-byte vectors
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(index.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
-              "cache_topk_wide: index and q must start 16-byte aligned");
-  const long long *rs = nullptr, *qsc = nullptr;
-  const int* re = nullptr;
-  if (scoped) {
-    check_cuda(*row_scope, "row_scope");
-    check_cuda(*row_expiry, "row_expiry");
-    check_cuda(*q_scope, "q_scope");
-    TORCH_CHECK(row_scope->scalar_type() == at::kLong && row_scope->dim() == 1 &&
-                    row_scope->size(0) == n_rows,
-                "row_scope must be int64[n_rows]");
-    TORCH_CHECK(row_expiry->scalar_type() == at::kInt && row_expiry->dim() == 1 &&
-                    row_expiry->size(0) == n_rows,
-                "row_expiry must be int32[n_rows]");
-    TORCH_CHECK(q_scope->scalar_type() == at::kLong && q_scope->dim() == 1 &&
-                    q_scope->size(0) == n_q,
-                "q_scope must be int64[n_q]");
-    TORCH_CHECK(row_scope->device() == index.device() &&
-                    row_expiry->device() == index.device() &&
-                    q_scope->device() == index.device(),
-                "cache_topk_wide: all tensors must be on one device");
-    TORCH_CHECK(row_scope->is_contiguous() && row_expiry->is_contiguous() &&
-                    q_scope->is_contiguous(),
-                "cache_topk_wide: tag tensors must be contiguous");
-    // the kernel reads a lane's 4 row tags as 16-byte vectors
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(row_scope->data_ptr()) % 32 == 0 &&
-                    reinterpret_cast<uintptr_t>(row_expiry->data_ptr()) % 16 == 0,
-                "row_scope/row_expiry must start 32/16-byte aligned (row 4k of the "
-                "allocation)");
-    TORCH_CHECK(now >= INT32_MIN && now <= INT32_MAX, "now must fit int32");
-    rs = reinterpret_cast<const long long*>(row_scope->data_ptr<int64_t>());
-    re = row_expiry->data_ptr<int32_t>();
-    qsc = reinterpret_cast<const long long*>(q_scope->data_ptr<int64_t>());
-  }
-  auto best = at::zeros({n_q}, at::TensorOptions().dtype(at::kLong).device(q.device()));
-  if (n_q == 0 || n_rows == 0)
-    return {best, at::full({n_q}, -1, best.options().dtype(at::kInt))};
-  int nw = scoped ? (int)now : 0;
-  if (fp8 && scoped)
-    launch_cache_topk_wide<CacheElemFp8, true>(index, q, rs, re, qsc, nw, best);
-  else if (fp8)
-    launch_cache_topk_wide<CacheElemFp8, false>(index, q, rs, re, qsc, nw, best);
-  else if (scoped)
-    launch_cache_topk_wide<CacheElemBf16, true>(index, q, rs, re, qsc, nw, best);
-  else
-    launch_cache_topk_wide<CacheElemBf16, false>(index, q, rs, re, qsc, nw, best);
-  auto hi = best.bitwise_right_shift(32).to(at::kLong);
-  auto idx = at::where(best == 0, -1, best.bitwise_and(0xFFFFFFFFLL)).to(at::kInt);
-  return {hi, idx};
-}
-
-// Wide rows, tiled (cache_wide_tiled_kernels.cuh): one launch for up to 256
-// queries, dynamic LDS sized by the call's query tiles.
-template <class E, bool SCOPED>
-static void launch_cache_topk_wide_tiled(const at::Tensor& index, const at::Tensor& q,
-                                         const long long* rs, const int* re,
-                                         const long long* qsc, int now, at::Tensor& best) {
-  using elem = typename E::elem;
-  long long n_rows = index.size(0);
-  int n_q = (int)q.size(0), dim = (int)q.size(1);
-  long long blocks = (n_rows + kWideTiledBlockRows - 1) / kWideTiledBlockRows;
-  auto kernel = &cache_topk_wide_tiled_kernel_t<E, SCOPED>;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, kWideLdsLimit);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256),
-                     (size_t)wide_tiled_lds_bytes<SCOPED>(n_q), current_stream(),
-                     reinterpret_cast<const elem*>(index.data_ptr()), n_rows,
-                     reinterpret_cast<const elem*>(q.data_ptr()), n_q, dim,
-                     reinterpret_cast<unsigned long long*>(best.data_ptr<int64_t>()), rs, re,
-                     qsc, now);
+  return cache_topk_wide_rows("cache_topk_wide", false, index, q, row_scope, row_expiry,
+                              q_scope, now);
 }
 
 // cache_topk_wide's arguments, checks and (hi, idx), from one pass over the
@@ -789,80 +688,8 @@ std::vector<at::Tensor> cache_topk_wide_tiled(at::Tensor index, at::Tensor q,
                                               c10::optional<at::Tensor> row_scope,
                                               c10::optional<at::Tensor> row_expiry,
                                               c10::optional<at::Tensor> q_scope, int64_t now) {
-  check_cuda(index, "index");
-  check_cuda(q, "q");
-  bool scoped = row_scope.has_value();
-  TORCH_CHECK(row_expiry.has_value() == scoped && q_scope.has_value() == scoped,
-              "cache_topk_wide_tiled: row_scope, row_expiry and q_scope are given together or "
-              "not at all");
-  bool fp8 = index.scalar_type() == at::kFloat8_e4m3fn;
-  TORCH_CHECK(index.scalar_type() == q.scalar_type(), "index/q dtype mismatch");
-  TORCH_CHECK(fp8 || index.scalar_type() == at::kBFloat16,
-              "bf16 or float8_e4m3fn required");
-  TORCH_CHECK(index.dim() == 2 && q.dim() == 2, "index and q must be 2-D");
-  TORCH_CHECK(index.is_contiguous() && q.is_contiguous(),
-              "cache_topk_wide_tiled: index and q must be contiguous");
-  long long n_rows = index.size(0);
-  int n_q = (int)q.size(0);
-  long long dim = q.size(1);
-  TORCH_CHECK(index.size(1) == dim, "dim mismatch");
-  TORCH_CHECK(dim % kWideChunk == 0 && dim > 512 && dim <= kWideMaxDim,
-              "cache_topk_wide_tiled: dim must be a multiple of 128 in 640..2048, got ", dim,
-              " (128..512: cache_topk, cache_topk_scoped)");
-  TORCH_CHECK(n_q <= 256, "cache_topk_wide_tiled: at most 256 queries per call");
-  TORCH_CHECK(q.device() == index.device(),
-              "cache_topk_wide_tiled: all tensors must be on one device");
-  // rows and queries are read as 16-byte vectors
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(index.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
-              "cache_topk_wide_tiled: index and q must start 16-byte aligned");
-  const long long *rs = nullptr, *qsc = nullptr;
-  const int* re = nullptr;
-  if (scoped) {
-    check_cuda(*row_scope, "row_scope");
-    check_cuda(*row_expiry, "row_expiry");
-    check_cuda(*q_scope, "q_scope");
-    TORCH_CHECK(row_scope->scalar_type() == at::kLong && row_scope->dim() == 1 &&
-                    row_scope->size(0) == n_rows,
-                "row_scope must be int64[n_rows]");
-    TORCH_CHECK(row_expiry->scalar_type() == at::kInt && row_expiry->dim() == 1 &&
-                    row_expiry->size(0) == n_rows,
-                "row_expiry must be int32[n_rows]");
-    TORCH_CHECK(q_scope->scalar_type() == at::kLong && q_scope->dim() == 1 &&
-                    q_scope->size(0) == n_q,
-                "q_scope must be int64[n_q]");
-    TORCH_CHECK(row_scope->device() == index.device() &&
-                    row_expiry->device() == index.device() &&
-                    q_scope->device() == index.device(),
-                "cache_topk_wide_tiled: all tensors must be on one device");
-    TORCH_CHECK(row_scope->is_contiguous() && row_expiry->is_contiguous() &&
-                    q_scope->is_contiguous(),
-                "cache_topk_wide_tiled: tag tensors must be contiguous");
-    // the kernel reads a lane's 4 row tags as 16-byte vectors
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(row_scope->data_ptr()) % 32 == 0 &&
-                    reinterpret_cast<uintptr_t>(row_expiry->data_ptr()) % 16 == 0,
-                "row_scope/row_expiry must start 32/16-byte aligned (row 4k of the "
-                "allocation)");
-    TORCH_CHECK(now >= INT32_MIN && now <= INT32_MAX, "now must fit int32");
-    rs = reinterpret_cast<const long long*>(row_scope->data_ptr<int64_t>());
-    re = row_expiry->data_ptr<int32_t>();
-    qsc = reinterpret_cast<const long long*>(q_scope->data_ptr<int64_t>());
-  }
-  auto best = at::zeros({n_q}, at::TensorOptions().dtype(at::kLong).device(q.device()));
-  if (n_q == 0 || n_rows == 0)
-    return {best, at::full({n_q}, -1, best.options().dtype(at::kInt))};
-  int nw = scoped ? (int)now : 0;
-  if (fp8 && scoped)
-    launch_cache_topk_wide_tiled<CacheElemFp8, true>(index, q, rs, re, qsc, nw, best);
-  else if (fp8)
-    launch_cache_topk_wide_tiled<CacheElemFp8, false>(index, q, rs, re, qsc, nw, best);
-  else if (scoped)
-    launch_cache_topk_wide_tiled<CacheElemBf16, true>(index, q, rs, re, qsc, nw, best);
-  else
-    launch_cache_topk_wide_tiled<CacheElemBf16, false>(index, q, rs, re, qsc, nw, best);
-  auto hi = best.bitwise_right_shift(32).to(at::kLong);
-  auto idx = at::where(best == 0, -1, best.bitwise_and(0xFFFFFFFFLL)).to(at::kInt);
-  return {hi, idx};
+  return cache_topk_wide_rows("cache_topk_wide_tiled", true, index, q, row_scope, row_expiry,
+                              q_scope, now);
 }
 
 // Queries one pass of cache_topk_wide holds: the constexpr its launch uses.
@@ -870,12 +697,9 @@ int64_t cache_wide_queries_per_pass(int64_t dim, bool fp8, bool scoped) {
   TORCH_CHECK(dim % kWideChunk == 0 && dim > 512 && dim <= kWideMaxDim,
               "cache_wide_queries_per_pass: dim must be a multiple of 128 in 640..2048, got ",
               dim);
-  int d = (int)dim;
-  if (fp8)
-    return scoped ? wide_queries_per_pass<CacheElemFp8, true>(d)
-                  : wide_queries_per_pass<CacheElemFp8, false>(d);
-  return scoped ? wide_queries_per_pass<CacheElemBf16, true>(d)
-                : wide_queries_per_pass<CacheElemBf16, false>(d);
+  return dispatch_elem_scoped(fp8, scoped, [&](auto e, auto sc) -> int64_t {
+    return wide_queries_per_pass<decltype(e), decltype(sc)::value>((int)dim);
+  });
 }
 
 // MXFP4 index rows from bf16 vectors: (packed u8 [n, dim/2], scale u8
@@ -905,143 +729,85 @@ std::vector<at::Tensor> mxfp4_quantize_rows(at::Tensor x) {
   return {packed, scale, inv_norm};
 }
 
-// Checks and launches shared by cache_topk_mxfp4 and cache_topk_mxfp4_scoped
-// (tags == nullptr: unfiltered). n_q <= 256 in two passes of <= 128.
+// MXFP4 index, 128..512 elements per row (mxfp4_kernels.cuh): n_q <= 256 in
+// two passes of <= 128.
 template <bool SCOPED>
-static std::vector<at::Tensor> cache_topk_mxfp4_impl(
-    const char* op, const at::Tensor& packed, const at::Tensor& scale,
-    const at::Tensor& inv_norm, const at::Tensor& q, const at::Tensor* row_scope,
-    const at::Tensor* row_expiry, const at::Tensor* q_scope, int64_t now) {
-  check_cuda(packed, "packed");
-  check_cuda(scale, "scale");
-  check_cuda(inv_norm, "inv_norm");
-  check_cuda(q, "q");
-  TORCH_CHECK(q.scalar_type() == at::kFloat8_e4m3fn && q.dim() == 2, op,
-              ": q must be float8_e4m3fn [n_q, dim]");
-  long long n_rows = packed.size(0);
-  int n_q = (int)q.size(0), dim = (int)q.size(1);
-  TORCH_CHECK(dim % 128 == 0 && dim >= 128 && dim <= 512, op, ": unsupported dim ", dim,
-              " (supported: 128/256/384/512)");
-  TORCH_CHECK(packed.scalar_type() == at::kByte && packed.dim() == 2 &&
-                  packed.size(1) == dim / 2,
-              op, ": packed must be uint8 [n_rows, dim/2]");
-  TORCH_CHECK(scale.scalar_type() == at::kByte && scale.dim() == 2 &&
-                  scale.size(0) == n_rows && scale.size(1) == dim / 32,
-              op, ": scale must be uint8 [n_rows, dim/32]");
-  TORCH_CHECK(inv_norm.scalar_type() == at::kFloat && inv_norm.dim() == 1 &&
-                  inv_norm.size(0) == n_rows,
-              op, ": inv_norm must be float32 [n_rows]");
-  TORCH_CHECK(n_q <= 256, op, ": at most 256 queries per call");
-  TORCH_CHECK(scale.device() == packed.device() && inv_norm.device() == packed.device() &&
-                  q.device() == packed.device(),
-              op, ": all tensors must be on one device");
-  // 16-byte row and query fragments, a dword of scale bytes per k-step,
-  // 16 bytes of inv_norm per 4 result rows
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(packed.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(scale.data_ptr()) % 4 == 0 &&
-                  reinterpret_cast<uintptr_t>(inv_norm.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
-              op, ": packed/inv_norm/q must start 16-byte and scale 4-byte aligned");
-  const long long* rs = nullptr;
-  const int* re = nullptr;
-  const long long* qsc = nullptr;
-  if (SCOPED) {
-    check_cuda(*row_scope, "row_scope");
-    check_cuda(*row_expiry, "row_expiry");
-    check_cuda(*q_scope, "q_scope");
-    TORCH_CHECK(row_scope->scalar_type() == at::kLong && row_scope->dim() == 1 &&
-                    row_scope->size(0) == n_rows,
-                "row_scope must be int64[n_rows]");
-    TORCH_CHECK(row_expiry->scalar_type() == at::kInt && row_expiry->dim() == 1 &&
-                    row_expiry->size(0) == n_rows,
-                "row_expiry must be int32[n_rows]");
-    TORCH_CHECK(q_scope->scalar_type() == at::kLong && q_scope->dim() == 1 &&
-                    q_scope->size(0) == n_q,
-                "q_scope must be int64[n_q]");
-    TORCH_CHECK(row_scope->device() == packed.device() &&
-                    row_expiry->device() == packed.device() &&
-                    q_scope->device() == packed.device(),
-                op, ": all tensors must be on one device");
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(row_scope->data_ptr()) % 32 == 0 &&
-                    reinterpret_cast<uintptr_t>(row_expiry->data_ptr()) % 16 == 0,
-                "row_scope/row_expiry must start 32/16-byte aligned (row 4k of the "
-                "allocation)");
-    TORCH_CHECK(now >= INT32_MIN && now <= INT32_MAX, "now must fit int32");
-    rs = reinterpret_cast<const long long*>(row_scope->data_ptr<int64_t>());
-    re = row_expiry->data_ptr<int32_t>();
-    qsc = reinterpret_cast<const long long*>(q_scope->data_ptr<int64_t>());
-  }
-  auto best = at::zeros({n_q}, at::TensorOptions().dtype(at::kLong).device(q.device()));
-  if (n_q == 0 || n_rows == 0)
-    return {best, at::full({n_q}, -1, best.options().dtype(at::kInt))};
-  constexpr int ROWTILES = 16;
-  long long blocks = (n_rows + 64 * ROWTILES - 1) / (64 * ROWTILES);
+static void launch_cache_topk_mxfp4(const char* op, const CacheShape& s,
+                                    const at::Tensor& packed, const at::Tensor& scale,
+                                    const at::Tensor& inv_norm, const at::Tensor& q,
+                                    const CacheTags& t, at::Tensor& best) {
+  long long blocks = (s.n_rows + 64 * kCacheRowTiles - 1) / (64 * kCacheRowTiles);
   auto* best_p = reinterpret_cast<unsigned long long*>(best.data_ptr<int64_t>());
   auto* q_base = reinterpret_cast<const uint8_t*>(q.data_ptr());
-  auto launch = [&](auto kernel, int q0) {
-    int kq = std::min(128, n_q - q0);
-    // blk_best (+ q_scope stage) + ceil(kq/16)*16 query rows of dim+16 bytes
-    size_t lds_bytes = (SCOPED ? 2 : 1) * 128 * 8 +
-                       (size_t)((kq + 15) / 16 * 16) * (dim + 16);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), lds_bytes,
-                       current_stream(), packed.data_ptr<uint8_t>(),
-                       scale.data_ptr<uint8_t>(), inv_norm.data_ptr<float>(), n_rows,
-                       q_base + (long long)q0 * dim, kq, best_p + q0, rs, re,
-                       SCOPED ? qsc + q0 : nullptr, (int)now);
-  };
-  for (int q0 = 0; q0 < n_q; q0 += 128) {
-    switch (dim >> 7) {
-      case 1: launch(&cache_topk_mxfp4_kernel_t<1, ROWTILES, SCOPED>, q0); break;
-      case 2: launch(&cache_topk_mxfp4_kernel_t<2, ROWTILES, SCOPED>, q0); break;
-      case 3: launch(&cache_topk_mxfp4_kernel_t<3, ROWTILES, SCOPED>, q0); break;
-      default: launch(&cache_topk_mxfp4_kernel_t<4, ROWTILES, SCOPED>, q0); break;
+  dispatch_ksteps(op, s.dim, [&](auto ks) {
+    // the kernel counts k-steps of 128 elements
+    auto kernel = &cache_topk_mxfp4_kernel_t<decltype(ks)::value / 4, kCacheRowTiles, SCOPED>;
+    for (int q0 = 0; q0 < s.n_q; q0 += 128) {
+      int kq = std::min(128, s.n_q - q0);
+      // blk_best (+ q_scope stage) + ceil(kq/16)*16 query rows of dim+16 bytes
+      size_t lds_bytes = (SCOPED ? 2 : 1) * 128 * 8 +
+                         (size_t)((kq + 15) / 16 * 16) * (s.dim + 16);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), lds_bytes,
+                         current_stream(), packed.data_ptr<uint8_t>(),
+                         scale.data_ptr<uint8_t>(), inv_norm.data_ptr<float>(), s.n_rows,
+                         q_base + (long long)q0 * s.dim, kq, best_p + q0, t.row_scope,
+                         t.row_expiry, SCOPED ? t.q_scope + q0 : nullptr, t.now);
     }
-  }
-  auto hi = best.bitwise_right_shift(32).to(at::kLong);
-  auto idx = at::where(best == 0, -1, best.bitwise_and(0xFFFFFFFFLL)).to(at::kInt);
-  return {hi, idx};
+  });
+}
+
+static std::vector<at::Tensor> cache_topk_mxfp4_narrow(
+    const char* op, const at::Tensor& packed, const at::Tensor& scale,
+    const at::Tensor& inv_norm, const at::Tensor& q, const OptTensor& row_scope,
+    const OptTensor& row_expiry, const OptTensor& q_scope, int64_t now) {
+  CacheShape s = check_cache_mxfp4(op, packed, scale, inv_norm, q, 128, 512);
+  CacheTags t = cache_tags(op, packed, s, row_scope, row_expiry, q_scope, now);
+  return cache_lookup(s, q, {s.n_q}, true, [&](at::Tensor& best) {
+    if (t.scoped)
+      launch_cache_topk_mxfp4<true>(op, s, packed, scale, inv_norm, q, t, best);
+    else
+      launch_cache_topk_mxfp4<false>(op, s, packed, scale, inv_norm, q, t, best);
+  });
 }
 
 std::vector<at::Tensor> cache_topk_mxfp4(at::Tensor packed, at::Tensor scale,
                                          at::Tensor inv_norm, at::Tensor q) {
-  return cache_topk_mxfp4_impl<false>("cache_topk_mxfp4", packed, scale, inv_norm, q,
-                                      nullptr, nullptr, nullptr, 0);
+  return cache_topk_mxfp4_narrow("cache_topk_mxfp4", packed, scale, inv_norm, q, c10::nullopt,
+                                 c10::nullopt, c10::nullopt, 0);
 }
 
 std::vector<at::Tensor> cache_topk_mxfp4_scoped(at::Tensor packed, at::Tensor scale,
                                                 at::Tensor inv_norm, at::Tensor q,
                                                 at::Tensor row_scope, at::Tensor row_expiry,
                                                 at::Tensor q_scope, int64_t now) {
-  return cache_topk_mxfp4_impl<true>("cache_topk_mxfp4_scoped", packed, scale, inv_norm, q,
-                                     &row_scope, &row_expiry, &q_scope, now);
+  return cache_topk_mxfp4_narrow("cache_topk_mxfp4_scoped", packed, scale, inv_norm, q,
+                                 row_scope, row_expiry, q_scope, now);
 }
 
 // Wide MXFP4 rows (mxfp4_wide_kernels.cuh): passes of the fp8 query block's
 // wide_queries_per_pass queries, each one launch that streams the whole index.
 template <bool SCOPED>
-static void launch_cache_topk_mxfp4_wide(const at::Tensor& packed, const at::Tensor& scale,
-                                         const at::Tensor& inv_norm, const at::Tensor& q,
-                                         const long long* rs, const int* re,
-                                         const long long* qsc, int now, at::Tensor& best) {
-  long long n_rows = packed.size(0);
-  int n_q = (int)q.size(0), dim = (int)q.size(1);
-  long long blocks = (n_rows + 64 * kMxWideRowTiles - 1) / (64 * kMxWideRowTiles);
+static void launch_cache_topk_mxfp4_wide(const CacheShape& s, const at::Tensor& packed,
+                                         const at::Tensor& scale, const at::Tensor& inv_norm,
+                                         const at::Tensor& q, const CacheTags& t,
+                                         at::Tensor& best) {
+  long long blocks = (s.n_rows + 64 * kMxWideRowTiles - 1) / (64 * kMxWideRowTiles);
   auto* q_base = reinterpret_cast<const uint8_t*>(q.data_ptr());
   auto* best_p = reinterpret_cast<unsigned long long*>(best.data_ptr<int64_t>());
   auto kernel = &cache_topk_mxfp4_wide_kernel_t<SCOPED>;
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
                             hipFuncAttributeMaxDynamicSharedMemorySize, kWideLdsLimit);
-  const int qb = wide_queries_per_pass<CacheElemFp8, SCOPED>(dim);
-  for (int q0 = 0; q0 < n_q; q0 += qb) {
-    int kq = std::min(qb, n_q - q0);
-    size_t lds_bytes = wide_lds_bytes<CacheElemFp8, SCOPED>(dim, kq);
+  const int qb = wide_queries_per_pass<CacheElemFp8, SCOPED>(s.dim);
+  for (int q0 = 0; q0 < s.n_q; q0 += qb) {
+    int kq = std::min(qb, s.n_q - q0);
+    size_t lds_bytes = wide_lds_bytes<CacheElemFp8, SCOPED>(s.dim, kq);
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), lds_bytes,
                        current_stream(), packed.data_ptr<uint8_t>(),
-                       scale.data_ptr<uint8_t>(), inv_norm.data_ptr<float>(), n_rows,
-                       q_base + (long long)q0 * dim, kq, dim, best_p + q0, rs, re,
-                       SCOPED ? qsc + q0 : nullptr, now);
+                       scale.data_ptr<uint8_t>(), inv_norm.data_ptr<float>(), s.n_rows,
+                       q_base + (long long)q0 * s.dim, kq, s.dim, best_p + q0, t.row_scope,
+                       t.row_expiry, SCOPED ? t.q_scope + q0 : nullptr, t.now);
   }
 }
 
@@ -1054,87 +820,14 @@ std::vector<at::Tensor> cache_topk_mxfp4_wide(at::Tensor packed, at::Tensor scal
                                               c10::optional<at::Tensor> q_scope,
                                               int64_t now) {
   const char* op = "cache_topk_mxfp4_wide";
-  check_cuda(packed, "packed");
-  check_cuda(scale, "scale");
-  check_cuda(inv_norm, "inv_norm");
-  check_cuda(q, "q");
-  bool scoped = row_scope.has_value();
-  TORCH_CHECK(row_expiry.has_value() == scoped && q_scope.has_value() == scoped, op,
-              ": row_scope, row_expiry and q_scope are given together or not at all");
-  TORCH_CHECK(q.scalar_type() == at::kFloat8_e4m3fn && q.dim() == 2, op,
-              ": q must be float8_e4m3fn [n_q, dim]");
-  int n_q = (int)q.size(0);
-  long long dim = q.size(1);
-  TORCH_CHECK(dim % 128 == 0 && dim > 512 && dim <= kWideMaxDim, op,
-              ": dim must be a multiple of 128 in 640..2048, got ", dim,
-              " (128..512: cache_topk_mxfp4, cache_topk_mxfp4_scoped)");
-  TORCH_CHECK(packed.scalar_type() == at::kByte && packed.dim() == 2 &&
-                  packed.size(1) == dim / 2,
-              op, ": packed must be uint8 [n_rows, dim/2]");
-  long long n_rows = packed.size(0);
-  TORCH_CHECK(scale.scalar_type() == at::kByte && scale.dim() == 2 &&
-                  scale.size(0) == n_rows && scale.size(1) == dim / 32,
-              op, ": scale must be uint8 [n_rows, dim/32]");
-  TORCH_CHECK(inv_norm.scalar_type() == at::kFloat && inv_norm.dim() == 1 &&
-                  inv_norm.size(0) == n_rows,
-              op, ": inv_norm must be float32 [n_rows]");
-  TORCH_CHECK(n_q <= 256, op, ": at most 256 queries per call");
-  TORCH_CHECK(scale.device() == packed.device() && inv_norm.device() == packed.device() &&
-                  q.device() == packed.device(),
-              op, ": all tensors must be on one device");
-  TORCH_CHECK(packed.is_contiguous() && scale.is_contiguous() && inv_norm.is_contiguous() &&
-                  q.is_contiguous(),
-              op, ": packed, scale, inv_norm and q must be contiguous");
-  // 16-byte row and query fragments, a dword of scale bytes per k-step,
-  // 16 bytes of inv_norm per 4 result rows
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(packed.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(scale.data_ptr()) % 4 == 0 &&
-                  reinterpret_cast<uintptr_t>(inv_norm.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
-              op, ": packed/inv_norm/q must start 16-byte and scale 4-byte aligned");
-  const long long *rs = nullptr, *qsc = nullptr;
-  const int* re = nullptr;
-  if (scoped) {
-    check_cuda(*row_scope, "row_scope");
-    check_cuda(*row_expiry, "row_expiry");
-    check_cuda(*q_scope, "q_scope");
-    TORCH_CHECK(row_scope->scalar_type() == at::kLong && row_scope->dim() == 1 &&
-                    row_scope->size(0) == n_rows,
-                "row_scope must be int64[n_rows]");
-    TORCH_CHECK(row_expiry->scalar_type() == at::kInt && row_expiry->dim() == 1 &&
-                    row_expiry->size(0) == n_rows,
-                "row_expiry must be int32[n_rows]");
-    TORCH_CHECK(q_scope->scalar_type() == at::kLong && q_scope->dim() == 1 &&
-                    q_scope->size(0) == n_q,
-                "q_scope must be int64[n_q]");
-    TORCH_CHECK(row_scope->device() == packed.device() &&
-                    row_expiry->device() == packed.device() &&
-                    q_scope->device() == packed.device(),
-                op, ": all tensors must be on one device");
-    TORCH_CHECK(row_scope->is_contiguous() && row_expiry->is_contiguous() &&
-                    q_scope->is_contiguous(),
-                op, ": tag tensors must be contiguous");
-    // the kernel reads a lane's 4 row tags as 16-byte vectors
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(row_scope->data_ptr()) % 32 == 0 &&
-                    reinterpret_cast<uintptr_t>(row_expiry->data_ptr()) % 16 == 0,
-                "row_scope/row_expiry must start 32/16-byte aligned (row 4k of the "
-                "allocation)");
-    TORCH_CHECK(now >= INT32_MIN && now <= INT32_MAX, "now must fit int32");
-    rs = reinterpret_cast<const long long*>(row_scope->data_ptr<int64_t>());
-    re = row_expiry->data_ptr<int32_t>();
-    qsc = reinterpret_cast<const long long*>(q_scope->data_ptr<int64_t>());
-  }
-  auto best = at::zeros({n_q}, at::TensorOptions().dtype(at::kLong).device(q.device()));
-  if (n_q == 0 || n_rows == 0)
-    return {best, at::full({n_q}, -1, best.options().dtype(at::kInt))};
-  if (scoped)
-    launch_cache_topk_mxfp4_wide<true>(packed, scale, inv_norm, q, rs, re, qsc, (int)now,
-                                       best);
-  else
-    launch_cache_topk_mxfp4_wide<false>(packed, scale, inv_norm, q, rs, re, qsc, 0, best);
-  auto hi = best.bitwise_right_shift(32).to(at::kLong);
-  auto idx = at::where(best == 0, -1, best.bitwise_and(0xFFFFFFFFLL)).to(at::kInt);
-  return {hi, idx};
+  CacheShape s = check_cache_mxfp4(op, packed, scale, inv_norm, q, 640, kWideMaxDim);
+  CacheTags t = cache_tags(op, packed, s, row_scope, row_expiry, q_scope, now);
+  return cache_lookup(s, q, {s.n_q}, true, [&](at::Tensor& best) {
+    if (t.scoped)
+      launch_cache_topk_mxfp4_wide<true>(s, packed, scale, inv_norm, q, t, best);
+    else
+      launch_cache_topk_mxfp4_wide<false>(s, packed, scale, inv_norm, q, t, best);
+  });
 }
 
 at::Tensor kv_score_assign(at::Tensor stats, at::Tensor pred_tokens, double w_kv,

@@ -238,144 +238,81 @@ __device__ __forceinline__ unsigned long long pack_score(float s, unsigned idx) 
   return ((unsigned long long)u << 32) | idx;
 }
 
-// fp8 LDS-staged variant — same structure as cache_topk_lds_kernel_t
-// below (query block in LDS, A-tile ping-pong, ks-outer interleave) with
-// 1-byte elements: the 128-query stage is only ~50 KB, so 3 CTAs/CU fit
-// and occupancy recovers on top of the latency fixes. Row stride padded
-// to KSTEPS*32+16 bytes (100 dwords = 36 mod 64 -> 16 distinct banks).
-template <int KSTEPS, int ROWTILES>
-__global__ void __launch_bounds__(256)
-cache_topk_fp8_lds_kernel_t(const uint8_t* __restrict__ index, long long n_rows,
-                            const uint8_t* __restrict__ q, int n_q /* <= 128 */,
-                            int dim, unsigned long long* __restrict__ best) {
-  constexpr int DIMP = KSTEPS * 32 + 16;
-  extern __shared__ unsigned char smem[];
-  uint8_t* qs = smem;
-  unsigned long long* blk_best =
-      reinterpret_cast<unsigned long long*>(smem + 128 * DIMP);
-  if (threadIdx.x < 128) blk_best[threadIdx.x] = 0;
-  int chunks_per_row = dim / 8;
-  for (int idx = threadIdx.x; idx < n_q * chunks_per_row; idx += 256) {
-    int r = idx / chunks_per_row, c = (idx - r * chunks_per_row) * 8;
-    *reinterpret_cast<long*>(&qs[r * DIMP + c]) =
-        *reinterpret_cast<const long*>(&q[(long long)r * dim + c]);
+// Element type of an index: what differs between the bf16 and the fp8
+// (OCP e4m3) lookup kernels. kPad is the query block's LDS row pad in
+// elements, chosen so the 16 query rows of a q-tile land on distinct banks:
+// bf16 rows of KSTEPS*32+8 halves are 4 mod 64 dwords -> banks 4*row mod 64;
+// fp8 rows of KSTEPS*32+16 bytes are 100 dwords = 36 mod 64 at dim 384 ->
+// 16 distinct banks.
+struct CacheElemBf16 {
+  using elem = bf16;
+  using frag = short8;  // 8 bf16 per lane per k-step
+  static constexpr int kPad = 8;
+  static __device__ __forceinline__ frag zero() { return frag{0, 0, 0, 0, 0, 0, 0, 0}; }
+  static __device__ __forceinline__ floatx4 mfma(frag a, frag b, floatx4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
   }
-  __syncthreads();
-  int wave = threadIdx.x >> 6;
-  int lane = threadIdx.x & 63;
-  int row = lane & 15;
-  int kgrp = lane >> 4;
-  auto load_tile = [&](long (&frag)[KSTEPS], int t) {
-    long long i0 = ((long long)blockIdx.x * 4 * ROWTILES + wave * ROWTILES + t) * 16;
-    bool i_ok = i0 < n_rows && (i0 + row) < n_rows;
-    #pragma unroll
-    for (int ks = 0; ks < KSTEPS; ++ks) {
-      int kk = ks * 32 + kgrp * 8;
-      frag[ks] = i_ok
-          ? *reinterpret_cast<const long*>(&index[(i0 + row) * dim + kk])
-          : 0L;
-    }
-  };
-  constexpr int QT = 8;
-  auto compute_tile = [&](long (&frag)[KSTEPS], int t) {
-    long long i0 = ((long long)blockIdx.x * 4 * ROWTILES + wave * ROWTILES + t) * 16;
-    if (i0 >= n_rows) return;
-    floatx4 acc[QT];
-    #pragma unroll
-    for (int qt = 0; qt < QT; ++qt) acc[qt] = floatx4{0.f, 0.f, 0.f, 0.f};
-    int qrow = min(row, n_q - 1);
-    #pragma unroll
-    for (int ks = 0; ks < KSTEPS; ++ks) {
-      int kk = ks * 32 + kgrp * 8;
-      #pragma unroll
-      for (int qt = 0; qt < QT; ++qt) {
-        long b = *reinterpret_cast<const long*>(&qs[(qt * 16 + qrow) * DIMP + kk]);
-        acc[qt] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(frag[ks], b, acc[qt], 0, 0, 0);
-      }
-    }
-    int lim = (int)min((long long)16, n_rows - i0);
-    #pragma unroll
-    for (int qt = 0; qt < QT; ++qt) {
-      int q0 = qt * 16;
-      bool q_in = (q0 + row) < n_q;
-      float best_s = -1e30f;
-      int best_r = 0;
-      #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float sc = (kgrp * 4 + r < lim) ? acc[qt][r] : -1e30f;
-        if (sc > best_s) { best_s = sc; best_r = r; }
-      }
-      long long irow = i0 + kgrp * 4 + best_r;
-      if (!q_in) best_s = -1e30f;
-      unsigned long long p = pack_score(best_s, (unsigned)(irow & 0xFFFFFFFF));
-      #pragma unroll
-      for (int off = 16; off < 64; off <<= 1) {
-        unsigned long long o = shfl_xor_u64(p, off);
-        if (o > p) p = o;
-      }
-      if (kgrp == 0 && q_in) atomicMax(&blk_best[q0 + row], p);
-    }
-  };
-  long frag_a[KSTEPS], frag_b[KSTEPS];
-  load_tile(frag_a, 0);
-  static_assert(ROWTILES % 2 == 0, "pipeline assumes even ROWTILES");
-  for (int t = 0; t < ROWTILES; t += 2) {
-    load_tile(frag_b, t + 1);
-    compute_tile(frag_a, t);
-    if (t + 2 < ROWTILES) load_tile(frag_a, t + 2);
-    compute_tile(frag_b, t + 1);
-  }
-  __syncthreads();
-  if (threadIdx.x < (unsigned)n_q && blk_best[threadIdx.x])
-    atomicMax(&best[threadIdx.x], blk_best[threadIdx.x]);
-}
+};
 
-// LDS-staged variant: PMC on the register-tile kernel above shows a
-// 27:1 SQ_WAIT:SQ_BUSY ratio — the serial L2 B-load -> MFMA dependency
-// chain in its query loop leaves waves stalled on ~300-cycle L2 hits.
-// Staging the whole (<=128-query) block in LDS once per CTA turns those
+struct CacheElemFp8 {
+  using elem = uint8_t;
+  using frag = long;  // 8 fp8 per lane per k-step
+  static constexpr int kPad = 16;
+  static __device__ __forceinline__ frag zero() { return 0L; }
+  static __device__ __forceinline__ floatx4 mfma(frag a, frag b, floatx4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a, b, c, 0, 0, 0);
+  }
+};
+
+// LDS-staged arg-max kernel: PMC on the register-tile kernel it replaced
+// shows a 27:1 SQ_WAIT:SQ_BUSY ratio — the serial L2 B-load -> MFMA
+// dependency chain in its query loop leaves waves stalled on ~300-cycle L2
+// hits. Staging the whole (<=128-query) block in LDS once per CTA turns those
 // into ~30-cycle ds_reads the scheduler hides behind MFMAs; the index
 // still streams HBM once per 128-query pass (the host chunks 256-query
-// calls into two passes). Row stride padded by 8 halves so the 16 query
-// rows of a q-tile land on distinct banks (KSTEPS*32+8 halves = 4 mod 64
-// dwords -> banks 4*row mod 64, conflict-free for 16 rows).
-template <int KSTEPS, int ROWTILES>
+// calls into two passes). The fp8 query stage is only ~50 KB, so 3 CTAs/CU
+// fit and occupancy recovers on top of the latency fixes.
+// Dynamic LDS: 128 * (KSTEPS*32 + kPad) * sizeof(elem) query block, then
+// 128 * 8 blk_best.
+template <class E, int KSTEPS, int ROWTILES>
 __global__ void __launch_bounds__(256)
-cache_topk_lds_kernel_t(const bf16* __restrict__ index, long long n_rows,
-                        const bf16* __restrict__ q, int n_q /* <= 128 */, int dim,
-                        unsigned long long* __restrict__ best) {
-  constexpr int DIMP = KSTEPS * 32 + 8;
+cache_topk_lds_kernel_t(const typename E::elem* __restrict__ index, long long n_rows,
+                        const typename E::elem* __restrict__ q, int n_q /* <= 128 */,
+                        int dim, unsigned long long* __restrict__ best) {
+  using elem = typename E::elem;
+  using frag_t = typename E::frag;
+  constexpr int DIMP = KSTEPS * 32 + E::kPad;
   extern __shared__ unsigned char smem[];
-  bf16* qs = reinterpret_cast<bf16*>(smem);
+  elem* qs = reinterpret_cast<elem*>(smem);
   unsigned long long* blk_best =
-      reinterpret_cast<unsigned long long*>(smem + 128 * DIMP * sizeof(bf16));
+      reinterpret_cast<unsigned long long*>(smem + 128 * DIMP * sizeof(elem));
   if (threadIdx.x < 128) blk_best[threadIdx.x] = 0;
   int chunks_per_row = dim / 8;
   for (int idx = threadIdx.x; idx < n_q * chunks_per_row; idx += 256) {
     int r = idx / chunks_per_row, c = (idx - r * chunks_per_row) * 8;
-    *reinterpret_cast<short8*>(&qs[r * DIMP + c]) =
-        *reinterpret_cast<const short8*>(&q[(long long)r * dim + c]);
+    *reinterpret_cast<frag_t*>(&qs[r * DIMP + c]) =
+        *reinterpret_cast<const frag_t*>(&q[(long long)r * dim + c]);
   }
   __syncthreads();
   int wave = threadIdx.x >> 6;
   int lane = threadIdx.x & 63;
   int row = lane & 15;
   int kgrp = lane >> 4;
-  // A-tile software pipeline: at 1 CTA/CU (the 100 KB query stage) a
+  // A-tile software pipeline: at 1 CTA/CU (the 100 KB bf16 query stage) a
   // wave that loads a row tile and only then computes exposes the full
   // HBM latency every tile. Ping-pong buffers (compile-time indexed —
   // rule #20) let tile t+1's 12 dwordx4 loads fly while tile t's 96
   // MFMAs issue.
-  auto load_tile = [&](short8 (&frag)[KSTEPS], int t) {
+  auto load_tile = [&](frag_t (&frag)[KSTEPS], int t) {
     long long i0 = ((long long)blockIdx.x * 4 * ROWTILES + wave * ROWTILES + t) * 16;
     bool i_ok = i0 < n_rows && (i0 + row) < n_rows;
     #pragma unroll
     for (int ks = 0; ks < KSTEPS; ++ks) {
       int kk = ks * 32 + kgrp * 8;
       if (i_ok)
-        frag[ks] = *reinterpret_cast<const short8*>(&index[(i0 + row) * dim + kk]);
+        frag[ks] = *reinterpret_cast<const frag_t*>(&index[(i0 + row) * dim + kk]);
       else
-        frag[ks] = short8{0, 0, 0, 0, 0, 0, 0, 0};
+        frag[ks] = E::zero();
     }
   };
   // ks-outer with one accumulator per query tile: at 1 CTA/CU the q-inner
@@ -383,7 +320,7 @@ cache_topk_lds_kernel_t(const bf16* __restrict__ index, long long n_rows,
   // dependency chain per q-tile, nothing else in flight); QT independent
   // chains issued back-to-back hide it completely.
   constexpr int QT = 8;  // 128 queries / 16
-  auto compute_tile = [&](short8 (&frag)[KSTEPS], int t) {
+  auto compute_tile = [&](frag_t (&frag)[KSTEPS], int t) {
     long long i0 = ((long long)blockIdx.x * 4 * ROWTILES + wave * ROWTILES + t) * 16;
     if (i0 >= n_rows) return;
     floatx4 acc[QT];
@@ -395,8 +332,8 @@ cache_topk_lds_kernel_t(const bf16* __restrict__ index, long long n_rows,
       int kk = ks * 32 + kgrp * 8;
       #pragma unroll
       for (int qt = 0; qt < QT; ++qt) {
-        short8 b = *reinterpret_cast<const short8*>(&qs[(qt * 16 + qrow) * DIMP + kk]);
-        acc[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag[ks], b, acc[qt], 0, 0, 0);
+        frag_t b = *reinterpret_cast<const frag_t*>(&qs[(qt * 16 + qrow) * DIMP + kk]);
+        acc[qt] = E::mfma(frag[ks], b, acc[qt]);
       }
     }
     int lim = (int)min((long long)16, n_rows - i0);
@@ -422,7 +359,7 @@ cache_topk_lds_kernel_t(const bf16* __restrict__ index, long long n_rows,
       if (kgrp == 0 && q_in) atomicMax(&blk_best[q0 + row], p);
     }
   };
-  short8 frag_a[KSTEPS], frag_b[KSTEPS];
+  frag_t frag_a[KSTEPS], frag_b[KSTEPS];
   load_tile(frag_a, 0);
   static_assert(ROWTILES % 2 == 0, "pipeline assumes even ROWTILES");
   for (int t = 0; t < ROWTILES; t += 2) {
@@ -437,36 +374,17 @@ cache_topk_lds_kernel_t(const bf16* __restrict__ index, long long n_rows,
 }
 
 // ---------------------------------------------------------------------------
-// 3b. Scope- and TTL-filtered variant of the two LDS-staged kernels above.
+// 3b. Scope- and TTL-filtered variant of the LDS-staged kernel above.
 //    Every index row carries a tag (scope id, expiry second); row r may
 //    answer query j iff
 //      row_expiry[r] > now && (q_scope[j] == 0 || row_scope[r] == q_scope[j])
 //    and ineligible rows are dropped before anything is reduced: filtering
 //    the argmax afterwards cannot bring back the eligible row it discarded.
-//    One template over the element type; the unfiltered kernels stay as
-//    they are (sibling, not a flag, so their code does not move). Same
-//    structure: query block in LDS, A-tile ping-pong, ks-outer MFMAs.
+//    A sibling of the unfiltered kernel, not a flag on it: that kernel's
+//    code does not move, and its tie rule differs (there the lower of a
+//    lane's four rows wins a tie, here the higher). Same structure: query
+//    block in LDS, A-tile ping-pong, ks-outer MFMAs.
 // ---------------------------------------------------------------------------
-
-struct CacheElemBf16 {
-  using elem = bf16;
-  using frag = short8;  // 8 bf16 per lane per k-step
-  static constexpr int kPad = 8;  // row pad in elements, see the kernels above
-  static __device__ __forceinline__ frag zero() { return frag{0, 0, 0, 0, 0, 0, 0, 0}; }
-  static __device__ __forceinline__ floatx4 mfma(frag a, frag b, floatx4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  }
-};
-
-struct CacheElemFp8 {
-  using elem = uint8_t;
-  using frag = long;  // 8 fp8 per lane per k-step
-  static constexpr int kPad = 16;
-  static __device__ __forceinline__ frag zero() { return 0L; }
-  static __device__ __forceinline__ floatx4 mfma(frag a, frag b, floatx4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a, b, c, 0, 0, 0);
-  }
-};
 
 // Tags of the lane's four index rows (i0 + kgrp*4 + r in the MFMA result
 // layout). Loaded raw in load_tile, next to the A-tile loads of the
