@@ -176,12 +176,8 @@ async def _run_shard(args, rank: int = 0, world: int = 1) -> None:
 
         from aigw.extproc.fast_front import FastFront
 
-        fast = FastFront(
-            server, runtime,
-            gpu_direct=bool(args.gpu and _torch.cuda.is_available()),
-            gpu_cache=bool(args.gpu and args.semantic_cache
-                           and _torch.cuda.is_available()),
-        )
+        fast = FastFront(server, runtime,
+                         **_fast_front_options(args, _torch.cuda.is_available()))
         port = await fast.start(args.host, port)
         reload_cbs.append(fast.reload)
 
@@ -248,6 +244,16 @@ async def _run_shard(args, rank: int = 0, world: int = 1) -> None:
         await front_cleanup()
 
 
+def _fast_front_options(args, has_gpu: bool) -> dict:
+    """What the command line hands the native front (--front fast)."""
+    return dict(
+        gpu_direct=bool(args.gpu and has_gpu),
+        gpu_cache=bool(args.gpu and args.semantic_cache and has_gpu),
+        # the in-process cache's index format (csrc/admission.hip)
+        cache_index_dtype=getattr(args, "cache_index_dtype", "bf16"),
+    )
+
+
 def _check_cache_flags(args) -> None:
     """Startup errors for semantic-cache flag combinations no front serves."""
     scoped = getattr(args, "cache_scope", "value") == "index"
@@ -261,11 +267,6 @@ def _check_cache_flags(args) -> None:
             "--semantic-cache-scope index and --semantic-cache-ttl are not "
             "supported by the native front (--front fast) yet: its in-process "
             "cache has no per-row scope or expiry — use --front lean")
-    if (args.front == "fast" and args.gpu and args.semantic_cache
-            and getattr(args, "cache_index_dtype", "bf16") == "mxfp4"):
-        from aigw.extproc.fast_front import MXFP4_NATIVE_FRONT
-
-        raise SystemExit(MXFP4_NATIVE_FRONT)
     candidates = getattr(args, "cache_candidates", 1)
     if not 1 <= candidates <= 8:
         raise SystemExit("--semantic-cache-candidates must be 1..8")
@@ -436,8 +437,7 @@ def main(argv=None) -> int:
                       default="bf16", dest="cache_index_dtype",
                       help="semantic-cache index precision (fp8 = 2x rows per GB, faster "
                            "lookups, ~1%% cosine error; mxfp4 = 3.7x rows per GB at "
-                           "dim 384, 4-bit MX blocks against fp8 queries, not served "
-                           "by --front fast)")
+                           "dim 384, 4-bit MX blocks against fp8 queries)")
     runp.add_argument("--semantic-cache-dim", type=int, default=384, dest="cache_dim",
                       metavar="N",
                       help="semantic-cache embedding and index row width: a multiple "

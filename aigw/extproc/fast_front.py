@@ -152,13 +152,6 @@ def build_fast_server(runtime: RuntimeConfig):
     return srv
 
 
-# the native server's in-process cache (csrc/admission.hip) stores bf16 or
-# fp8 rows only
-MXFP4_NATIVE_FRONT = (
-    "--cache-index-dtype mxfp4 is not supported by the native front "
-    "(--front fast): its in-process cache has no MXFP4 index — use --front lean")
-
-
 class FastFront:
     """Lifecycle wrapper: fallback aiohttp app + native server + a
     metrics bridge exposing the native counters on the Python /metrics."""
@@ -170,8 +163,6 @@ class FastFront:
                  cache_threshold: float = 0.92, cache_seed: int = 7,
                  cache_index_dtype: str = "bf16",
                  n_merges: int = 32768, tokenizer_seed: int = 1355):
-        if gpu_cache and cache_index_dtype == "mxfp4":
-            raise ValueError(MXFP4_NATIVE_FRONT)
         # `server` is the Python GatewayServer used for cold paths
         self.py_server = server
         self.runtime = runtime
@@ -230,7 +221,8 @@ class FastFront:
                     emb.view(_t.uint16).numpy(), proj.view(_t.uint16).numpy(),
                     dim=dim, capacity=self.cache_capacity,
                     threshold=self.cache_threshold,
-                    fp8=self.cache_index_dtype == "fp8")
+                    fp8=self.cache_index_dtype == "fp8",
+                    mxfp4=self.cache_index_dtype == "mxfp4")
         sockets = ([self.gpu_socket] if isinstance(self.gpu_socket, str)
                    else list(self.gpu_socket or []))
         for s in sockets:

@@ -32,6 +32,7 @@
 
 #include "bpe_kernels.cuh"
 #include "cache_kernels.cuh"
+#include "admission_mxfp4_kernels.cuh"
 
 namespace aigw_fast {
 
@@ -412,24 +413,37 @@ class GpuAdmissionDirect {
 
   bool init_cache(const uint16_t* emb, int vocab, const uint16_t* proj,
                   int dim, long long capacity, float threshold,
-                  int pending_cap, bool fp8) {
+                  int pending_cap, bool fp8, bool mxfp4) {
     if (!ready_ || dim != 384) return false;  // one tuned topk instantiation
+    if (fp8 && mxfp4) return false;           // one index format
     HIP_OK(hipSetDevice(device_));
     dim_ = dim;
     cap_ = capacity;
     threshold_ = threshold;
     vocab_ = vocab;
     pending_cap_ = pending_cap;
-    fp8_ = fp8;
+    fmt_ = mxfp4 ? IndexFormat::kMxfp4 : fp8 ? IndexFormat::kFp8 : IndexFormat::kBf16;
     HIP_OK(hipMalloc(&d_emb_, sizeof(bf16) * (size_t)vocab * dim));
     HIP_OK(hipMemcpy(d_emb_, emb, sizeof(bf16) * (size_t)vocab * dim,
                      hipMemcpyHostToDevice));
     HIP_OK(hipMalloc(&d_proj_, sizeof(bf16) * (size_t)dim * dim));
     HIP_OK(hipMemcpy(d_proj_, proj, sizeof(bf16) * (size_t)dim * dim,
                      hipMemcpyHostToDevice));
-    size_t elt = fp8 ? 1 : sizeof(bf16);
-    HIP_OK(hipMalloc(&d_index_, elt * (size_t)capacity * dim));
-    HIP_OK(hipMemset(d_index_, 0, elt * (size_t)capacity * dim));
+    if (mxfp4) {
+      // packed nibbles in d_index_, one E8M0 byte per 32 elements, one fp32
+      // inv_norm per row; scale 127 (2^0) and inv_norm 0 make an unwritten
+      // row score 0, as aigw.ops.semcache.SemanticCache initialises them
+      HIP_OK(hipMalloc(&d_index_, (size_t)capacity * (dim / 2)));
+      HIP_OK(hipMemset(d_index_, 0, (size_t)capacity * (dim / 2)));
+      HIP_OK(hipMalloc(&d_scale_, (size_t)capacity * (dim / 32)));
+      HIP_OK(hipMemset(d_scale_, 127, (size_t)capacity * (dim / 32)));
+      HIP_OK(hipMalloc(&d_inv_norm_, sizeof(float) * (size_t)capacity));
+      HIP_OK(hipMemset(d_inv_norm_, 0, sizeof(float) * (size_t)capacity));
+    } else {
+      size_t elt = fp8 ? 1 : sizeof(bf16);
+      HIP_OK(hipMalloc(&d_index_, elt * (size_t)capacity * dim));
+      HIP_OK(hipMemset(d_index_, 0, elt * (size_t)capacity * dim));
+    }
     HIP_OK(hipMalloc(&d_pending_, sizeof(bf16) * (size_t)pending_cap * dim));
     HIP_OK(hipStreamCreateWithFlags(&insert_stream_, hipStreamNonBlocking));
     for (int s = 0; s < kSets; ++s) {
@@ -439,7 +453,7 @@ class GpuAdmissionDirect {
       HIP_OK(hipMalloc(&b.d_poolbf, sizeof(bf16) * (size_t)max_req_ * dim));
       HIP_OK(hipMalloc(&b.d_gout, sizeof(float) * (size_t)max_req_ * dim));
       HIP_OK(hipMalloc(&b.d_q, sizeof(bf16) * (size_t)max_req_ * dim));
-      if (fp8) HIP_OK(hipMalloc(&b.d_q8, (size_t)max_req_ * dim));
+      if (fp8 || mxfp4) HIP_OK(hipMalloc(&b.d_q8, (size_t)max_req_ * dim));
       HIP_OK(hipMalloc(&b.d_best, sizeof(unsigned long long) * max_req_));
       HIP_OK(hipHostMalloc(&b.h_best, sizeof(unsigned long long) * max_req_,
                            hipHostMallocDefault));
@@ -491,21 +505,46 @@ class GpuAdmissionDirect {
     hipLaunchKernelGGL(gemm_bf16_nt_kernel, ggrid, dim3(256), 0, st,
                        b.d_poolbf, d_proj_, b.d_gout, n_req, dim, dim,
                        nullptr, 0);
-    hipLaunchKernelGGL(l2norm_rows_kernel, dim3(n_req), dim3(dim), 0, st,
-                       b.d_gout, b.d_q, n_req, dim);
+    const bool mxfp4 = fmt_ == IndexFormat::kMxfp4;
+    if (!mxfp4)
+      hipLaunchKernelGGL(l2norm_rows_kernel, dim3(n_req), dim3(dim), 0, st,
+                         b.d_gout, b.d_q, n_req, dim);
     // park query vectors for possible insert: one gather launch
     memcpy(b.h_slots, pending_slots, sizeof(int32_t) * (size_t)n_req);
     HIP_OK(hipMemcpyAsync(b.d_slots, b.h_slots, sizeof(int32_t) * n_req,
                           hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(park_pending_kernel, dim3(n_req), dim3(dim), 0, st,
-                       b.d_q, b.d_slots, n_req, dim, d_pending_);
+    if (mxfp4)
+      // l2norm, park and the e4m3 query in one launch (a wave per request)
+      hipLaunchKernelGGL(mxfp4_query_tail_kernel, dim3((n_req + 3) / 4),
+                         dim3(256), 0, st, b.d_gout, b.d_slots, n_req, b.d_q,
+                         b.d_q8, d_pending_);
+    else
+      hipLaunchKernelGGL(park_pending_kernel, dim3(n_req), dim3(dim), 0, st,
+                         b.d_q, b.d_slots, n_req, dim, d_pending_);
     long long rows_now = rows_visible_.load(std::memory_order_acquire);
     b.rows_in_flight = rows_now;
     if (rows_now > 0) {
       HIP_OK(hipMemsetAsync(b.d_best, 0, sizeof(unsigned long long) * n_req, st));
       constexpr int ROWTILES = 16;
       long long blocks = (rows_now + 64 * ROWTILES - 1) / (64 * ROWTILES);
-      if (fp8_) {
+      if (mxfp4) {
+        // 208 B per row; the query block is sized by ceil(kq/16) tiles, as
+        // the Python op's launcher (csrc/aigw_kernels.hip) sizes it
+        auto kernel = &cache_topk_mxfp4_kernel_t<3, ROWTILES, false>;
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  160 * 1024);
+        for (int q0 = 0; q0 < n_req; q0 += 128) {
+          int kq = (n_req - q0) < 128 ? (n_req - q0) : 128;
+          size_t lds = 128 * 8 + (size_t)((kq + 15) / 16 * 16) * (dim + 16);
+          hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), lds, st,
+                             (const uint8_t*)d_index_, (const uint8_t*)d_scale_,
+                             (const float*)d_inv_norm_, rows_now,
+                             (const uint8_t*)b.d_q8 + (size_t)q0 * dim, kq,
+                             b.d_best + q0, (const long long*)nullptr,
+                             (const int*)nullptr, (const long long*)nullptr, 0);
+        }
+      } else if (fmt_ == IndexFormat::kFp8) {
         // fp8 index streams HBM at half the bytes per row (2x rows in
         // the 288 GB budget)
         hipLaunchKernelGGL(bf16_to_fp8_kernel,
@@ -563,7 +602,13 @@ class GpuAdmissionDirect {
       return -1;
     long long row = head_;
     head_ = (head_ + 1) % cap_;
-    if (fp8_) {
+    if (fmt_ == IndexFormat::kMxfp4) {
+      hipLaunchKernelGGL(mxfp4_ring_insert_kernel, dim3(1), dim3(64), 0,
+                         insert_stream_,
+                         d_pending_ + (size_t)pending_slot * dim_, row,
+                         (uint8_t*)d_index_, d_scale_, d_inv_norm_);
+      if (hipGetLastError() != hipSuccess) return -1;
+    } else if (fmt_ == IndexFormat::kFp8) {
       hipLaunchKernelGGL(bf16_to_fp8_kernel, dim3((dim_ / 2 + 255) / 256),
                          dim3(256), 0, insert_stream_,
                          d_pending_ + (size_t)pending_slot * dim_,
@@ -607,7 +652,7 @@ class GpuAdmissionDirect {
     if (cache_on_) {
       (void)hipStreamDestroy(insert_stream_);
       for (void* p : {(void*)d_emb_, (void*)d_proj_, (void*)d_index_,
-                      (void*)d_pending_})
+                      (void*)d_scale_, (void*)d_inv_norm_, (void*)d_pending_})
         (void)hipFree(p);
     }
     for (void* p : {(void*)d_htab_keys_, (void*)d_htab_rank_})
@@ -627,10 +672,13 @@ class GpuAdmissionDirect {
   long long head_ = 0;  // writers hold the caller's insert mutex
   std::atomic<long long> rows_visible_{0};  // read lock-free by the batcher
   float threshold_ = 0.f;
-  bool fp8_ = false;
+  enum class IndexFormat { kBf16, kFp8, kMxfp4 };
+  IndexFormat fmt_ = IndexFormat::kBf16;
   bf16* d_emb_ = nullptr;
   bf16* d_proj_ = nullptr;
-  void* d_index_ = nullptr;
+  void* d_index_ = nullptr;       // rows; packed nibbles for mxfp4
+  uint8_t* d_scale_ = nullptr;    // mxfp4 only: E8M0 byte per 32 elements
+  float* d_inv_norm_ = nullptr;   // mxfp4 only: 1 / |dequantised row|
   bf16* d_pending_ = nullptr;
   hipStream_t insert_stream_{};
   size_t max_bytes_ = 0;
@@ -663,9 +711,10 @@ void admission_destroy(GpuAdmissionDirect* a) { delete a; }
 
 bool admission_init_cache(GpuAdmissionDirect* a, const uint16_t* emb, int vocab,
                           const uint16_t* proj, int dim, long long capacity,
-                          float threshold, int pending_cap, bool fp8) {
+                          float threshold, int pending_cap, bool fp8,
+                          bool mxfp4) {
   return a->init_cache(emb, vocab, proj, dim, capacity, threshold, pending_cap,
-                       fp8);
+                       fp8, mxfp4);
 }
 
 bool admission_count_lookup(GpuAdmissionDirect* a, const char* bytes, size_t n,

@@ -28,7 +28,8 @@ bool admission_count(GpuAdmissionDirect* a, const char* bytes, size_t n,
 void admission_destroy(GpuAdmissionDirect* a);
 bool admission_init_cache(GpuAdmissionDirect* a, const uint16_t* emb, int vocab,
                           const uint16_t* proj, int dim, long long capacity,
-                          float threshold, int pending_cap, bool fp8);
+                          float threshold, int pending_cap, bool fp8,
+                          bool mxfp4 = false);
 bool admission_count_lookup(GpuAdmissionDirect* a, const char* bytes, size_t n,
                             const int64_t* offsets, int n_req,
                             int32_t* counts_out, const int32_t* pending_slots,
@@ -75,7 +76,7 @@ class AdmissionProbe {
   }
 
   void init_cache(py::buffer emb, py::buffer proj, long long capacity,
-                  float threshold, int pending_cap, bool fp8) {
+                  float threshold, int pending_cap, bool fp8, bool mxfp4) {
     constexpr int dim = 384;  // the native cache's one tuned top-k shape
     py::buffer_info ei = emb.request();
     py::buffer_info pi = proj.request();
@@ -88,9 +89,11 @@ class AdmissionProbe {
     if (capacity <= 0 || pending_cap <= 0)
       throw std::runtime_error("capacity and pending_cap must be positive");
     if (cache_on_) throw std::runtime_error("cache already initialised");
+    if (fp8 && mxfp4)
+      throw std::runtime_error("fp8 and mxfp4 are two index formats: pick one");
     if (!admission_init_cache(adm_, static_cast<const uint16_t*>(ei.ptr), vocab,
                               static_cast<const uint16_t*>(pi.ptr), dim,
-                              capacity, threshold, pending_cap, fp8))
+                              capacity, threshold, pending_cap, fp8, mxfp4))
       throw std::runtime_error("native cache init failed");
     pending_cap_ = pending_cap;
     cache_on_ = true;
@@ -259,7 +262,7 @@ PYBIND11_MODULE(aigw_fast, m) {
            py::arg("max_req"), py::arg("device") = 0)
       .def("init_cache", &AdmissionProbe::init_cache, py::arg("emb_u16"),
            py::arg("proj_u16"), py::arg("capacity"), py::arg("threshold"),
-           py::arg("pending_cap"), py::arg("fp8"))
+           py::arg("pending_cap"), py::arg("fp8"), py::arg("mxfp4") = false)
       .def("count", &AdmissionProbe::count, py::arg("texts"))
       .def("count_lookup", &AdmissionProbe::count_lookup, py::arg("texts"),
            py::arg("slots") = py::none())
@@ -438,7 +441,7 @@ PYBIND11_MODULE(aigw_fast, m) {
       .def(
           "enable_gpu_direct_cache",
           [](FastServer& s, py::buffer emb, py::buffer proj, int dim,
-             long long capacity, float threshold, bool fp8) {
+             long long capacity, float threshold, bool fp8, bool mxfp4) {
             py::buffer_info ei = emb.request();
             py::buffer_info pi = proj.request();
             if (ei.itemsize != 2 || pi.itemsize != 2)
@@ -446,15 +449,18 @@ PYBIND11_MODULE(aigw_fast, m) {
             int vocab = (int)(ei.size / dim);
             if ((long long)vocab * dim != ei.size || pi.size != (long long)dim * dim)
               throw std::runtime_error("emb/proj shape mismatch");
+            if (fp8 && mxfp4)
+              throw std::runtime_error(
+                  "fp8 and mxfp4 are two index formats: pick one");
             if (!s.enable_gpu_direct_cache(
                     static_cast<const uint16_t*>(ei.ptr), vocab,
                     static_cast<const uint16_t*>(pi.ptr), dim, capacity,
-                    threshold, fp8))
+                    threshold, fp8, mxfp4))
               throw std::runtime_error("native cache init failed");
           },
           py::arg("emb"), py::arg("proj"), py::arg("dim") = 384,
           py::arg("capacity") = 65536, py::arg("threshold") = 0.92,
-          py::arg("fp8") = false)
+          py::arg("fp8") = false, py::arg("mxfp4") = false)
       .def("start", &FastServer::start, py::arg("host"), py::arg("port"),
            py::call_guard<py::gil_scoped_release>())
       .def("stop", &FastServer::stop, py::call_guard<py::gil_scoped_release>())

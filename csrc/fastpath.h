@@ -124,7 +124,7 @@ class FastServer {
   bool enable_gpu_direct_cache(const uint16_t* emb, int vocab,
                                const uint16_t* proj, int dim,
                                long long capacity, float threshold,
-                               bool fp8);
+                               bool fp8, bool mxfp4 = false);
 
   // lifecycle
   int start(const std::string& host, uint16_t port);  // returns bound port

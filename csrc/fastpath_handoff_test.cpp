@@ -95,7 +95,8 @@ bool admission_count(GpuAdmissionDirect* a, const char* bytes, size_t n,
          admission_wait(a, 0, n_req, counts_out, nullptr, nullptr);
 }
 bool admission_init_cache(GpuAdmissionDirect*, const uint16_t*, int,
-                          const uint16_t*, int, long long, float, int, bool) {
+                          const uint16_t*, int, long long, float, int, bool,
+                          bool) {
   return false;
 }
 bool admission_count_lookup(GpuAdmissionDirect* a, const char* bytes, size_t n,

@@ -25,16 +25,18 @@ typedef __attribute__((ext_vector_type(8))) int mx_int8;
 // kernel's bit-exact outputs must not depend on.
 // ---------------------------------------------------------------------------
 
-__global__ void __launch_bounds__(256)
-mxfp4_quantize_rows_kernel(const bf16* __restrict__ x, long long n, int dim,
-                           uint8_t* __restrict__ packed, uint8_t* __restrict__ scale,
-                           float* __restrict__ inv_norm) {
-  long long r = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
-  if (r >= n) return;  // wave-uniform
+// The wave's work on one row, given the row's own pointers; shared with the
+// native cache's ring insert (admission_mxfp4_kernels.cuh). PUBLISH orders
+// the row's stores for a concurrent lookup: nibbles and scales, a device-wide
+// fence, inv_norm last.
+template <bool PUBLISH>
+__device__ __forceinline__ void mxfp4_quantize_row(
+    const bf16* __restrict__ x, int dim, uint8_t* __restrict__ packed,
+    uint8_t* __restrict__ scale, float* __restrict__ inv_norm) {
   int lane = threadIdx.x & 63;
   bool on = lane * 8 < dim;
   short8 raw = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (on) raw = *reinterpret_cast<const short8*>(&x[r * dim + lane * 8]);
+  if (on) raw = *reinterpret_cast<const short8*>(&x[lane * 8]);
   // |bf16| bit patterns order like the magnitudes they encode
   int am = 0;
   #pragma unroll
@@ -74,12 +76,23 @@ mxfp4_quantize_rows_kernel(const bf16* __restrict__ x, long long n, int dim,
     ss = fmaf(d, d, ss);
   }
   if (on) {
-    *reinterpret_cast<unsigned*>(&packed[r * (dim / 2) + lane * 4]) = word;
-    if ((lane & 3) == 0) scale[r * (dim / 32) + (lane >> 2)] = (uint8_t)(e + 127);
+    *reinterpret_cast<unsigned*>(&packed[lane * 4]) = word;
+    if ((lane & 3) == 0) scale[lane >> 2] = (uint8_t)(e + 127);
   }
   #pragma unroll
   for (int off = 1; off < 64; off <<= 1) ss += __shfl_xor(ss, off);
-  if (lane == 0) inv_norm[r] = ss > 0.f ? ldexpf(rsqrtf(ss), -emax) : 0.f;
+  if (PUBLISH) __threadfence();
+  if (lane == 0) *inv_norm = ss > 0.f ? ldexpf(rsqrtf(ss), -emax) : 0.f;
+}
+
+__global__ void __launch_bounds__(256)
+mxfp4_quantize_rows_kernel(const bf16* __restrict__ x, long long n, int dim,
+                           uint8_t* __restrict__ packed, uint8_t* __restrict__ scale,
+                           float* __restrict__ inv_norm) {
+  long long r = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
+  if (r >= n) return;  // wave-uniform
+  mxfp4_quantize_row<false>(x + r * dim, dim, packed + r * (dim / 2),
+                            scale + r * (dim / 32), inv_norm + r);
 }
 
 // Wide rows: dim a multiple of 128 in 640..2048. Still one wave per row; the
