@@ -5,11 +5,13 @@
 // hardware, one host process decodes ~900 MB/s and sharding hosts
 // thrashes GPU contexts (4 processes: 36k -> 10k req/s). This module
 // removes the whole detour: the C++ gateway owns ONE HIP stream and
-// launches the same gfx950 BPE kernels (csrc/bpe_kernels.cuh) directly —
-// pack texts into a pinned staging buffer, one H2D copy, the sync-free
-// segmentation/scan/merge pipeline (device-resident totals, every kernel
-// self-bounds), one D2H of per-request counts, one event wait. Zero
-// Python, zero IPC, zero extra GPU contexts.
+// launches the same gfx950 BPE merge kernel (csrc/bpe_kernels.cuh)
+// directly — pack texts into a pinned staging buffer, H2D copies of text
+// and offsets, the sync-free pipeline of four kernels (flags and group
+// heads in one pass, one scan, one compaction: csrc/
+// admission_front_kernels.cuh; then the merge kernel; device-resident
+// totals, every kernel self-bounds), one D2H of per-request counts, one
+// event wait. Zero Python, zero IPC, zero extra GPU contexts.
 //
 // The merge table is supplied by the caller (aigw.ops.tokenizer
 // make_merges) so counts stay bit-identical to the Python/CPU oracle.
@@ -31,6 +33,7 @@
 #include <vector>
 
 #include "bpe_kernels.cuh"
+#include "admission_front_kernels.cuh"
 #include "cache_kernels.cuh"
 #include "admission_mxfp4_kernels.cuh"
 
@@ -221,10 +224,12 @@ class GpuAdmissionDirect {
     int32_t* h_slots = nullptr;
     uint8_t* d_bytes = nullptr;
     int64_t* d_off = nullptr;
-    uint8_t* d_flags = nullptr;
-    uint8_t* d_gflags = nullptr;
-    int32_t* d_blk = nullptr;
-    int32_t* d_excl = nullptr;
+    uint8_t* d_flags = nullptr;   // bit 0 segment start, bit 1 group head
+    uint8_t* d_gflags = nullptr;  // cache tail: token flags
+    int32_t* d_blk = nullptr;     // per-block segment counts, their scan;
+    int32_t* d_excl = nullptr;    // the cache tail reuses both
+    int32_t* d_gblk = nullptr;    // per-block group-head counts, their scan
+    int32_t* d_gexcl = nullptr;
     int32_t* d_totals = nullptr;
     int32_t* d_seg_start = nullptr;
     int32_t* d_seg_req = nullptr;
@@ -279,6 +284,8 @@ class GpuAdmissionDirect {
       HIP_OK(hipMalloc(&b.d_gflags, max_bytes));
       HIP_OK(hipMalloc(&b.d_blk, sizeof(int32_t) * max_blocks));
       HIP_OK(hipMalloc(&b.d_excl, sizeof(int32_t) * max_blocks));
+      HIP_OK(hipMalloc(&b.d_gblk, sizeof(int32_t) * max_blocks));
+      HIP_OK(hipMalloc(&b.d_gexcl, sizeof(int32_t) * max_blocks));
       HIP_OK(hipMalloc(&b.d_totals, sizeof(int32_t) * 2));
       HIP_OK(hipMalloc(&b.d_seg_start, sizeof(int32_t) * max_bytes));
       HIP_OK(hipMalloc(&b.d_seg_req, sizeof(int32_t) * max_bytes));
@@ -324,25 +331,24 @@ class GpuAdmissionDirect {
     HIP_OK(hipMemcpyAsync(b.d_off, b.h_off, sizeof(int64_t) * (size_t)n_req,
                           hipMemcpyHostToDevice, st));
     int blocks = (int)((n + 255) / 256);
-    // fused front end: class-rule flags + forced request starts + block
-    // counts in one pass; it also zeroes d_counts for the BPE kernel
-    hipLaunchKernelGGL(seg_flags_count_kernel, dim3(blocks), dim3(256), 0, st,
-                       b.d_bytes, (int)n, b.d_off, n_req, b.d_flags, b.d_blk,
+    // front end, three kernels (csrc/admission_front_kernels.cuh):
+    // class-rule flags + forced request starts + group heads + both block
+    // counts in one pass over the bytes (every flags[i < n] is written,
+    // so the buffer needs no clearing; it also zeroes d_counts for the
+    // BPE kernel), one scan launch for both count arrays
+    // (d_totals[0] = segments, d_totals[1] = groups), one compaction
+    // pass for seg_start, seg_req and ghead
+    hipLaunchKernelGGL(aigw_front::front_flags_kernel, dim3(blocks),
+                       dim3(aigw_front::kTile), 0, st, b.d_bytes, (int)n,
+                       b.d_off, n_req, b.d_flags, b.d_blk, b.d_gblk,
                        b.d_counts);
-    hipLaunchKernelGGL(excl_scan_kernel, dim3(1), dim3(256), 0, st,
-                       b.d_blk, blocks, b.d_excl, b.d_totals);
-    hipLaunchKernelGGL(seg_write_kernel, dim3(blocks), dim3(256), 0, st,
-                       b.d_flags, (int)n, b.d_excl, b.d_off, n_req,
-                       b.d_seg_start, b.d_seg_req);
-    // groups (device-bounded; every gflags[i < n] is written, 0 beyond
-    // n_segs, so the buffer needs no clearing)
-    hipLaunchKernelGGL(group_flags_count_kernel, dim3(blocks), dim3(256), 0,
-                       st, b.d_seg_start, b.d_seg_req, b.d_totals, b.d_off,
-                       (int)n, b.d_gflags, b.d_blk);
-    hipLaunchKernelGGL(excl_scan_kernel, dim3(1), dim3(256), 0, st,
-                       b.d_blk, blocks, b.d_excl, b.d_totals + 1);
-    hipLaunchKernelGGL(flag_compact_write_kernel, dim3(blocks), dim3(256), 0,
-                       st, b.d_gflags, (int)n, b.d_excl, b.d_ghead);
+    hipLaunchKernelGGL(aigw_front::dual_excl_scan_kernel, dim3(2), dim3(256), 0,
+                       st, b.d_blk, b.d_gblk, blocks, b.d_excl, b.d_gexcl,
+                       b.d_totals);
+    hipLaunchKernelGGL(aigw_front::front_write_kernel, dim3(blocks),
+                       dim3(aigw_front::kTile), 0, st, b.d_flags, (int)n,
+                       b.d_excl, b.d_gexcl, b.d_off, n_req, b.d_seg_start,
+                       b.d_seg_req, b.d_ghead);
     bool want_cache = pending_slots != nullptr && cache_on_;
     // the cache pipeline finds tokens by out_ids >= 0: merged-away byte
     // positions must read -1, not whatever the previous batch left there
@@ -641,6 +647,7 @@ class GpuAdmissionDirect {
       (void)hipHostFree(b.h_slots);
       for (void* p : {(void*)b.d_bytes, (void*)b.d_off, (void*)b.d_flags,
                       (void*)b.d_gflags, (void*)b.d_blk, (void*)b.d_excl,
+                      (void*)b.d_gblk, (void*)b.d_gexcl,
                       (void*)b.d_totals, (void*)b.d_seg_start,
                       (void*)b.d_seg_req, (void*)b.d_ghead,
                       (void*)b.d_out_ids, (void*)b.d_counts, (void*)b.d_pool,
