@@ -37,6 +37,7 @@
 
 #include "msgpack_mini.h"
 #include "native_core.h"
+#include "wake_tree.h"
 
 namespace aigw_fast {
 
@@ -701,14 +702,14 @@ class DirectGpuBatcher {
   // pointers only and pack is the one copy between extraction and H2D.
   // Ownership of `text`: the batcher thread may read it only between
   // dequeue and the end of pack; the request thread may touch it only
-  // after it has observed `done` under `m` (collect() hands the buffer
-  // back then). A request thread whose collect() timed out with `done`
-  // still false must not touch it and just drops its reference.
-  struct Waiter2 {
-    std::mutex m;
-    std::condition_variable cv;
+  // after it has seen DONE in `state` with acquire, i.e. after
+  // wake_tree::await() returned true (collect() hands the buffer back
+  // then). The same holds for the result fields: the batcher writes them
+  // with plain stores before it sets DONE with release. A request thread
+  // whose collect() ran into its deadline has seen no DONE: it must not
+  // touch text or results and just drops its reference.
+  struct Waiter2 : wake_tree::Node {
     std::string text;
-    bool done = false;
     int64_t count = 0;
     int32_t row = -1;
     float score = 0.f;
@@ -753,9 +754,8 @@ class DirectGpuBatcher {
                       std::string* reclaim = nullptr) {
     CacheLookup out;
     if (w == nullptr) return out;
-    std::unique_lock<std::mutex> lk(w->m);
-    w->cv.wait_for(lk, std::chrono::seconds(30), [&] { return w->done; });
-    if (w->done && reclaim != nullptr) {
+    if (!wake_tree::await(w.get(), std::chrono::seconds(30))) return out;
+    if (reclaim != nullptr) {
       reclaim->swap(w->text);
       reclaim->clear();
     }
@@ -820,9 +820,11 @@ class DirectGpuBatcher {
  private:
   // Two-deep software pipeline over the two admission BatchSets: while
   // batch N runs on set s's stream, batch N+1 is collected, packed, and
-  // submitted on set 1-s. The GPU pipeline is launch/latency-bound per
-  // batch (~1.5 ms), so overlapping whole batches (plus the CPU-side
-  // pack/fulfill work) nearly doubles admission throughput under load.
+  // submitted on set 1-s. A count-only batch keeps the GPU busy for about
+  // 100 us and the batcher's own cycle is longer than that
+  // (profiles/admission_fulfil.md), so overlapping whole batches with the
+  // CPU-side pack/fulfill work nearly doubles admission throughput under
+  // load.
   struct InFlight {
     std::vector<std::shared_ptr<Waiter2>> waiters;
     std::vector<int32_t> slots;
@@ -836,14 +838,14 @@ class DirectGpuBatcher {
     InFlight& fl = inflight_[s];
     if (!fl.valid) return;
     int n = (int)fl.waiters.size();
-    std::vector<int32_t> counts((size_t)n, 0);
-    std::vector<int32_t> rows((size_t)n, -1);
-    std::vector<float> scores((size_t)n, 0.f);
+    counts_.assign((size_t)n, 0);
+    rows_.assign((size_t)n, -1);
+    scores_.assign((size_t)n, 0.f);
     bool want_cache = cache_on_.load();
     int64_t w0 = now_us();
-    if (!admission_wait(adm_, s, n, counts.data(),
-                        want_cache ? rows.data() : nullptr,
-                        want_cache ? scores.data() : nullptr))
+    if (!admission_wait(adm_, s, n, counts_.data(),
+                        want_cache ? rows_.data() : nullptr,
+                        want_cache ? scores_.data() : nullptr))
       stats_errors++;
     int64_t w1 = now_us();
     stats_wait_us += (uint64_t)(w1 - w0);
@@ -854,20 +856,15 @@ class DirectGpuBatcher {
     uint64_t prev = stats_max_us.load();
     while ((uint64_t)bt > prev &&
            !stats_max_us.compare_exchange_weak(prev, (uint64_t)bt)) {}
-    for (int i = 0; i < n; ++i) {
-      auto& w = fl.waiters[i];
-      {
-        std::lock_guard<std::mutex> lk(w->m);
-        w->count = counts[i];
-        w->row = rows[i];
-        w->score = scores[i];
-        w->slot = fl.slots[i];
-        w->done = true;
-      }
-      // notify after unlocking so the woken thread does not block on
-      // w->m straight away; fl.waiters keeps the waiter alive across it
-      w->cv.notify_all();
-    }
+    // one futex wake per sleeping waiter, none for one that collects later;
+    // fl.waiters keeps each waiter alive across its wake
+    wake_tree::publish(fl.waiters.data(), (size_t)n,
+                       [&](size_t i, Waiter2& w) {
+                         w.count = counts_[i];
+                         w.row = rows_[i];
+                         w.score = scores_[i];
+                         w.slot = fl.slots[i];
+                       });
     stats_fulfill_us += (uint64_t)(now_us() - w1);
     fl.waiters.clear();
     fl.slots.clear();
@@ -935,7 +932,8 @@ class DirectGpuBatcher {
         used += take_n;
       }
       size_t nt = waiters.size();
-      std::vector<int32_t> slots((size_t)nt, -1);
+      std::vector<int32_t>& slots = inflight_[next_set].slots;
+      slots.assign(nt, -1);  // cleared by finish_set; keeps its capacity
       if (cache_on_) {
         std::lock_guard<std::mutex> lk(slot_mu_);
         for (size_t i = 0; i < nt && !free_slots_.empty(); ++i) {
@@ -952,21 +950,14 @@ class DirectGpuBatcher {
       stats_submit_us += (uint64_t)(now_us() - s0);
       if (!ok) {
         if (used > 0) stats_errors++;
-        for (size_t i = 0; i < nt; ++i) {
-          auto& w = waiters[i];
-          {
-            std::lock_guard<std::mutex> lk(w->m);
-            w->slot = slots[i];
-            w->done = true;
-          }
-          w->cv.notify_all();
-        }
+        wake_tree::publish(waiters.data(), nt,
+                           [&](size_t i, Waiter2& w) { w.slot = slots[i]; });
         waiters.clear();
+        slots.clear();
         continue;
       }
       InFlight& fl = inflight_[next_set];
       fl.waiters.swap(waiters);  // fl.waiters was cleared by finish_set
-      fl.slots = std::move(slots);
       fl.t0 = now_us();
       fl.valid = true;
       // overlap: retire the OLDER batch while this one runs on the GPU
@@ -985,13 +976,7 @@ class DirectGpuBatcher {
       q_.clear();
       q_bytes_ = 0;
     }
-    for (auto& w : all) {
-      {
-        std::lock_guard<std::mutex> lk(w->m);
-        w->done = true;
-      }
-      w->cv.notify_all();
-    }
+    wake_tree::publish(all.data(), all.size(), [](size_t, Waiter2&) {});
   }
 
   GpuAdmissionDirect* adm_ = nullptr;
@@ -1023,6 +1008,10 @@ class DirectGpuBatcher {
   std::vector<std::shared_ptr<Waiter2>> q_;  // each waiter owns its text
   size_t q_bytes_ = 0;                       // sum of queued text sizes
   InFlight inflight_[2];
+  // finish_set's result buffers (batcher thread only); members so that a
+  // batch allocates nothing
+  std::vector<int32_t> counts_, rows_;
+  std::vector<float> scores_;
   std::thread worker_;
 };
 
@@ -1269,9 +1258,10 @@ class ConnHandler {
         // fallback + rate-limit charge), so enqueue now and collect in
         // finish_usage — measured 112.6k -> 124.4k req/s. Unary keeps
         // the synchronous wait: deferring it measured 116.7k -> 107.4k
-        // @ p99 2.1 ms, because the ~1 ms admission sleep paces the
-        // 128 relay threads under the CPU quota (without it they all
-        // stay runnable and earn CFS throttling).
+        // @ p99 2.1 ms, because the admission sleep (then ~1 ms, a few
+        // hundred us since) paces the 128 relay threads under the CPU
+        // quota (without it they all stay runnable and earn CFS
+        // throttling).
         pending_count_ = srv_->gpu_direct_->enqueue(std::move(sc.text));
       } else {
         gpu_tokens = srv_->gpu_direct_ != nullptr
